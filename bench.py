@@ -1,9 +1,14 @@
 #!/usr/bin/env python
 """Benchmark: ET-QM9 (128 channels, 8 layers, 64 RBF, cutoff 5) energy + forces, molecules/s.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode infer|train]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode infer|train] [--dump-outputs DIR] [--full]
   (N > 1 without a launcher: bench.py starts N rank processes itself through torch.distributed.run
    before anything touches a GPU; under torchrun, WORLD_SIZE must equal N)
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (metric, value, unit,
+ms_per_step, ...).  --dump-outputs DIR also writes what the last timed step returned (infer: y.npy and
+neg_dy.npy, train: loss.npy; float32) into DIR; the inputs and weights are seeded, so two builds run
+with the same arguments can be compared output for output.  Everything else below runs only with --full.
 
 One step = TorchMD_Net.forward with derivative=True (y and -dy/dpos, create_graph=True exactly as
 reference models/model.py:286-298) on a batch of 32 synthetic QM9-like molecules resident in HBM
@@ -11,7 +16,9 @@ reference models/model.py:286-298) on a batch of 32 synthetic QM9-like molecules
 adds the force-matching loss, double backward, the fused RCCL gradient all-reduce and AdamW.
 Weak scaling: every rank processes its own batch; value = molecules of all ranks / max-rank time.
 
-Also reported (rank 0):
+With --full, also reported (rank 0; each leg has its own --no-... switch):
+  secondary    -- the other configurations (TensorNet C3, the training steps, fit() on the data path,
+                  ET-SPICE C4, TorchScript, the C5 water boxes).
   ddp_train    -- the data-parallel TRAINING step at this N: ET-SPICE C4, 16 x 40
                   atoms per GPU, E+F loss, forces with create_graph, double backward, ONE fused RCCL
                   all-reduce of the gradients, fused AdamW; HIP-graph replay of fwd + double backward on
@@ -19,7 +26,8 @@ Also reported (rank 0):
   roofline     -- the ET edge-aggregation kernel (tmdnet_et_message_fwd) on a C5-scale periodic
                   water box (50,001 atoms, ~2.7 M edges), HIP events on the launching stream;
                   algorithmic bytes per launch = E*(20 + 16H) + N*(48H + 4)  (SURVEY.md §8(d)).
-  roofline_c2  -- the same kernel live inside the timed region of the metric workload.
+  roofline_c2  -- the same kernel live in the metric workload (eager / train mode: inside the timed
+                  region, also without --full; hip-graph mode: a short eager pass after it).
   cpu_baseline -- oracle/model_oracle.py (plain PyTorch-CPU restatement of the reference) on the
                   same 32 molecules and weights, host cores of this box, bounded sample (N=1 only).
 """
@@ -67,7 +75,15 @@ def parse():
     ap.add_argument("--cpu-extra-seconds", type=float, default=6.0,
                     help="CPU sample per extra baseline config (C2 training, C3, C4, C5 1500-atom box)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary lines, ddp_train, the roofline / MFMA probes "
+                         "and the CPU baseline (each still subject to its --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def qm9_like(n_mol, gen_seed):
@@ -760,6 +776,25 @@ def phase(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, arrays, rank):
+    """--dump-outputs: the tensors the last timed step returned as out_dir/<name>.npy (rank r > 0:
+    <name>_rank<r>.npy), float32 (float64 stays float64).  An array over its share of DUMP_MAX_BYTES is
+    written as a fixed sample of its flattened elements (seeded index set, ascending order)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach().to("cpu")
+        x = (t if t.dtype == torch.float64 else t.float()).contiguous().numpy()
+        if x.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, share // x.itemsize, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ("" if rank == 0 else f"_rank{rank}") + ".npy"), x)
+
+
 def timed_loop(step, warmup, steps, ws, dev):
     for _ in range(warmup):
         step()
@@ -1360,7 +1395,7 @@ def main():
         trainer = LNNPStep(model, lr=4e-4, group=None)
 
         def step():
-            trainer.step(zd, posd, batchd, y_lab, f_lab)
+            return trainer.step(zd, posd, batchd, y_lab, f_lab)
     elif a.eager:
         def step():
             y, f = model(zd, posd, batchd)
@@ -1388,16 +1423,20 @@ def main():
     torch.cuda.synchronize()
     barrier(ws)
     t0 = time.perf_counter()
+    last = None
     for _ in range(a.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     barrier(ws)
     el = time.perf_counter() - t0
     kernels.EVENT_PROBE = None
     el = max_over_ranks(el, ws, dev)
+    if a.dump_outputs:  # (before anything below runs the model again: a replay's outputs are static buffers)
+        dump_outputs(a.dump_outputs, {"loss": last} if a.mode == "train" else {"y": last[0], "neg_dy": last[1]}, rank)
     if a.mode == "infer" and not a.eager:
         gm.check_capacity()
         gm.release()
+    if a.full and a.mode == "infer" and not a.eager:
         # graph replays run no Python: time the edge kernel live in a short eager pass instead
         probe = []
         kernels.EVENT_PROBE = probe
@@ -1441,7 +1480,7 @@ def main():
                               "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": None,
                               "bytes_per_launch": nbytes, "ms_per_launch": round(ms, 5),
                               "launches": len(probe)}
-    if a.mode == "infer" and not a.no_secondary:
+    if a.full and a.mode == "infer" and not a.no_secondary:
         phase("secondary: TensorNet C3")
         sec = {"tensornet_c3": secondary_tensornet(a, ws, rank, dev)}
         phase("secondary: ET training step")
@@ -1462,12 +1501,12 @@ def main():
         sec["tn_water_box_c5"] = secondary_tn_water_box(a, ws, rank, dev)
         if rank == 0:
             out["secondary"] = sec
-    if a.mode == "infer" and a.ddp_train:
+    if a.full and a.mode == "infer" and a.ddp_train:
         phase("ddp_train: ET-SPICE graphed training step")
         dt = ddp_train(a, ws, rank, dev)
         if rank == 0:
             out["ddp_train"] = dt
-    if rank == 0 and not a.no_roofline:
+    if a.full and rank == 0 and not a.no_roofline:
         phase("roofline probe (C5 water box)")
         # the secondary lines leave tens of GB in the caching allocator's segments: hand them back so
         # the probe's 10+ GB of inputs are laid out as in a fresh process
@@ -1492,7 +1531,7 @@ def main():
         E_c5 = int(out["roofline"]["workload"].split("E=")[1].split(",")[0])
         E_c2, N_c2 = (int(probe[0][2]), int(probe[0][3])) if probe else (12548, 678)
         out["mfma"] = mfma_probe(E_c5, a.roofline_atoms, E_c2, N_c2, a.channels, 64, dev)
-    if rank == 0 and ws == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and ws == 1 and not a.no_cpu_baseline:
         phase("CPU baseline")
         out["cpu_baseline"] = cpu_baseline(model, args, z, pos, batch, a.cpu_seconds)
         if a.cpu_extra_seconds > 0:
