@@ -37,7 +37,7 @@ def test_gemm_x3_epilogue_matches_fp64(K, N, wsplit, monkeypatch):
     rs = torch.rand(M, device=DEV, generator=g)
     C = torch.empty(M, N, device=DEV)
     pre = torch.empty(M, N, device=DEV)
-    assert kernels.gemm_ex_launch([{"A": A, "B": W, "bias": b, "C": C, "pre": pre, "act": 1, "rscale": rs}])
+    assert kernels.gemm_ex_launch(kernels.Gemm(A, W, True, b, C, False, act=1, pre=pre, rscale=rs))
     ref = A.double() @ W.double().t() + b.double()
     assert _rel(pre, ref) < 2e-6
     assert _rel(C, torch.nn.functional.silu(ref) * rs.double().view(-1, 1)) < 2e-6
@@ -45,7 +45,7 @@ def test_gemm_x3_epilogue_matches_fp64(K, N, wsplit, monkeypatch):
     G = torch.randn(M, N, device=DEV, generator=g)
     D = torch.randn(M, K, device=DEV, generator=g)
     out = torch.empty(M, K, device=DEV)
-    assert kernels.gemm_ex_launch([{"A": G, "B": W, "trans_b": False, "C": out, "dpre": D}])
+    assert kernels.gemm_ex_launch(kernels.Gemm(G, W, False, None, out, False, dpre=D))
     s = torch.sigmoid(D.double())
     ref = (G.double() @ W.double()) * (s * (1 + D.double() * (1 - s)))
     assert _rel(out, ref) < 2e-6

@@ -40,20 +40,20 @@ def main():
         tb = not mode.endswith("_t") and mode != "dpre"
         W = torch.randn(N, K, device=dev, generator=g) / K ** 0.5 if tb else torch.randn(K, N, device=dev, generator=g)
         C = torch.empty(M, N, device=dev)
-        p = {"A": A, "B": W, "trans_b": tb, "C": C}
+        p = kernels.Gemm(A, W, tb, None, C, False)
         nb = 4 * (M * K + M * N)
         if mode.startswith("act"):
-            p.update(bias=torch.randn(N, device=dev, generator=g), pre=torch.empty(M, N, device=dev), act=1)
+            p = p._replace(bias=torch.randn(N, device=dev, generator=g), pre=torch.empty(M, N, device=dev), act=1)
             nb += 4 * M * N
             if mode == "act_scale":
-                p["rscale"] = torch.rand(M, device=dev, generator=g)
+                p = p._replace(rscale=torch.rand(M, device=dev, generator=g))
         elif mode == "dpre":
-            p["dpre"] = torch.randn(M, N, device=dev, generator=g)
+            p = p._replace(dpre=torch.randn(M, N, device=dev, generator=g))
             nb += 4 * M * N
         elif mode == "bias":
-            p["bias"] = torch.randn(N, device=dev, generator=g)
-        assert kernels.gemm_ex_launch([p])
-        t = timed(lambda: kernels.gemm_ex_launch([p]))
+            p = p._replace(bias=torch.randn(N, device=dev, generator=g))
+        assert kernels.gemm_ex_launch(p)
+        t = timed(lambda: kernels.gemm_ex_launch(p))
         print(json.dumps({"shape": name, "M": M, "N": N, "K": K, "us": round(t, 1), "TBps": round(nb / t / 1e6, 2),
                           "bf16_TFs": round(12 * M * N * K / t / 1e6, 1)}), flush=True)
         del A, W, C, p

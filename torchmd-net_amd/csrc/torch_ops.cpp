@@ -31,7 +31,9 @@
 #include <torch/custom_class.h>
 #include <torch/library.h>
 
+#include <algorithm>
 #include <cmath>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -1113,93 +1115,91 @@ constexpr double kLnEps = 1e-5;  // nn.LayerNorm default (reference torchmd_et.p
 
 int64_t stack_np(bool hk, bool hv) { return 11 + 2 * int64_t(hk) + 2 * int64_t(hv); }
 
-// Large-row fp32 GEMM on tmdnet_gemm_x3_f32 (kernels.gemm_x3): B split per call (a [N][K] weight with
-// trans_b, a [K][N] right operand without); false when outside its envelope
-bool gemm_x3_into(const Tensor& A, const Tensor& B, bool trans_b, const Tensor& bias, const Tensor& C, bool beta) {
-  const int M = static_cast<int>(A.size(0)), N = static_cast<int>(C.size(1)), K = static_cast<int>(A.size(1));
-  auto al = [](const Tensor& t) { return !t.defined() || reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; };
-  if (!(A.scalar_type() == at::kFloat && B.scalar_type() == at::kFloat && C.scalar_type() == at::kFloat && M > 0 &&
-        K % 32 == 0 && N % 16 == 0 && A.stride(1) == 1 && B.stride(1) == 1 && C.stride(1) == 1 &&
-        A.stride(0) % 4 == 0 && B.stride(0) % 4 == 0 && C.stride(0) % 4 == 0 && al(A) && al(B) && al(C) &&
-        (!bias.defined() || (bias.is_contiguous() && al(bias)))))
-    return false;
-  void* st = stream_of(A);
+// One dense problem C = A op(B) (+ bias) (+ C if beta): kernels.Gemm without the epilogue fields
+struct GemmP {
+  Tensor A, B;
+  bool trans_b;
+  Tensor bias, C;
+  bool beta;
+  int M() const { return static_cast<int>(A.size(0)); }
+  int N() const { return static_cast<int>(C.size(1)); }
+  int K() const { return static_cast<int>(A.size(1)); }
+};
+
+bool al16(const Tensor& t) { return !t.defined() || reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
+bool rows16(const Tensor& t) { return t.stride(0) % 4 == 0 && al16(t); }  // 16-byte accesses along its rows
+
+// The envelopes, as kernels._operands_ok (a plain problem's part of it), kernels.grouped_ok and kernels.x3_ok
+bool operands_ok(const GemmP& p) {
+  return p.A.scalar_type() == at::kFloat && p.B.scalar_type() == at::kFloat && p.C.scalar_type() == at::kFloat &&
+         p.A.stride(1) == 1 && p.B.stride(1) == 1 && p.C.stride(1) == 1 &&
+         (!p.bias.defined() || p.bias.is_contiguous());
+}
+bool grouped_ok(const GemmP& p) {
+  return p.M() > 0 && p.M() <= 16384 && p.N() > 0 && p.K() > 0 && p.K() % 16 == 0 && operands_ok(p) &&
+         rows16(p.A) && (!p.trans_b || rows16(p.B));
+}
+bool x3_ok(const GemmP& p) {
+  return p.M() > 0 && p.K() % 32 == 0 && p.N() % 16 == 0 && operands_ok(p) && rows16(p.A) && rows16(p.B) &&
+         rows16(p.C) && al16(p.bias);
+}
+
+// n <= 4 problems in one tmdnet_gemm_f32 launch (kernels.gemm_launch); false, nothing launched, outside its envelope
+bool gemm_grouped_into(const GemmP* ps, int n) {
+  int dims[32];
+  const void* ptrs[16];
+  for (int i = 0; i < n; ++i) {
+    const GemmP& p = ps[i];
+    if (n > 4 || !grouped_ok(p)) return false;
+    const int d[8] = {p.M(), p.N(), p.K(), static_cast<int>(p.A.stride(0)), static_cast<int>(p.B.stride(0)),
+                      static_cast<int>(p.C.stride(0)), int(p.trans_b), int(p.beta)};
+    std::copy(d, d + 8, dims + 8 * i);
+    const void* q[4] = {p.A.data_ptr(), p.B.data_ptr(), p.bias.defined() ? p.bias.data_ptr() : nullptr, p.C.data_ptr()};
+    std::copy(q, q + 4, ptrs + 4 * i);
+  }
+  const int rc = n > 0 ? tmdnet_gemm_f32(n, dims, ptrs, stream_of(ps[0].A)) : TMDNET_UNSUPPORTED;
+  if (rc != TMDNET_UNSUPPORTED) check(rc, "tmdnet_gemm_f32");
+  return rc != TMDNET_UNSUPPORTED;
+}
+
+// One problem on tmdnet_gemm_x3_f32 (kernels.gemm_x3): B split per call (a [N][K] weight with trans_b, a [K][N]
+// right operand without); false when outside its envelope
+bool gemm_x3_into(const GemmP& p) {
+  if (!x3_ok(p)) return false;
+  const int N = p.N(), K = p.K(), ldb = static_cast<int>(p.B.stride(0));
+  void* st = stream_of(p.A);
   // (a split launch per call, as kernels.X3_WSPLIT = "launch": faster at C5 than the in-kernel split of
   // tmdnet_gemm_x3w_f32, and nothing cached)
-  Tensor bp = at::empty({3, N, K}, A.options().dtype(at::kShort));
-  int rc = trans_b ? tmdnet_proj_split_f32(N, K, B.data_ptr(), static_cast<int>(B.stride(0)), bp.data_ptr(), st)
-                   : tmdnet_split_t_f32(N, K, B.data_ptr(), static_cast<int>(B.stride(0)), bp.data_ptr(), st);
+  Tensor bp = at::empty({3, N, K}, p.A.options().dtype(at::kShort));
+  int rc = p.trans_b ? tmdnet_proj_split_f32(N, K, p.B.data_ptr(), ldb, bp.data_ptr(), st)
+                     : tmdnet_split_t_f32(N, K, p.B.data_ptr(), ldb, bp.data_ptr(), st);
   if (rc == TMDNET_UNSUPPORTED) return false;
   check(rc, "tmdnet_split");
-  rc = tmdnet_gemm_x3_f32(M, N, K, A.data_ptr(), static_cast<int>(A.stride(0)), bp.data_ptr(),
-                          bias.defined() ? bias.data_ptr() : nullptr, C.data_ptr(), static_cast<int>(C.stride(0)),
-                          beta ? 1 : 0, st);
-  if (rc == TMDNET_UNSUPPORTED) return false;
-  check(rc, "tmdnet_gemm_x3_f32");
-  return true;
+  rc = tmdnet_gemm_x3_f32(p.M(), N, K, p.A.data_ptr(), static_cast<int>(p.A.stride(0)), bp.data_ptr(),
+                          p.bias.defined() ? p.bias.data_ptr() : nullptr, p.C.data_ptr(),
+                          static_cast<int>(p.C.stride(0)), p.beta ? 1 : 0, st);
+  if (rc != TMDNET_UNSUPPORTED) check(rc, "tmdnet_gemm_x3_f32");
+  return rc != TMDNET_UNSUPPORTED;
 }
 
-// C = A op(B) (+ bias) (+ C if beta) on the hand-written grouped GEMM (up to 16384 rows) or the x3 GEMM
-// (more rows), the library outside both envelopes
-void gemm_into(const Tensor& A, const Tensor& B, bool trans_b, const Tensor& bias, const Tensor& C, bool beta) {
-  const int M = static_cast<int>(A.size(0)), N = static_cast<int>(C.size(1)), K = static_cast<int>(A.size(1));
-  if (M > 16384 && gemm_x3_into(A, B, trans_b, bias, C, beta)) return;
-  if (A.scalar_type() == at::kFloat && M > 0 && M <= 16384 && A.stride(1) == 1 && B.stride(1) == 1 &&
-      C.stride(1) == 1) {
-    int dims[8] = {M, N, K, static_cast<int>(A.stride(0)), static_cast<int>(B.stride(0)),
-                   static_cast<int>(C.stride(0)), int(trans_b), int(beta)};
-    const void* ptrs[4] = {A.data_ptr(), B.data_ptr(), bias.defined() ? bias.data_ptr() : nullptr, C.data_ptr()};
-    const int rc = tmdnet_gemm_f32(1, dims, ptrs, stream_of(A));
-    if (rc != TMDNET_UNSUPPORTED) {
-      check(rc, "tmdnet_gemm_f32");
-      return;
+// The router (kernels.gemm_group): the group in one grouped launch when every problem fits that kernel (the layer's
+// [q|k|v]^T and vec_proj^T input gradients: 8 launches fewer per C2 force pass); otherwise per problem the x3 GEMM
+// above 16384 rows, a grouped launch of its own at or below, and the library (kernels.gemm_lib) for the rest
+void gemm_group_into(std::initializer_list<GemmP> ps) {
+  const int n = static_cast<int>(ps.size());
+  if (gemm_grouped_into(ps.begin(), n)) return;
+  for (const GemmP& p : ps) {
+    if (p.M() > 16384 ? gemm_x3_into(p) : (n > 1 && gemm_grouped_into(&p, 1))) continue;
+    Tensor Bop = p.trans_b ? p.B.t() : p.B, C = p.C;
+    if (p.beta) {
+      C.addmm_(p.A, Bop);
+      if (p.bias.defined()) C.add_(p.bias);
+    } else if (p.bias.defined()) {
+      at::addmm_out(C, p.bias, p.A, Bop);
+    } else {
+      at::mm_out(C, p.A, Bop);
     }
   }
-  Tensor Bop = trans_b ? B.t() : B;
-  if (beta) {
-    C.addmm_(A, Bop);
-    if (bias.defined()) C.add_(bias);
-  } else if (bias.defined()) {
-    at::addmm_out(const_cast<Tensor&>(C), bias, A, Bop);
-  } else {
-    at::mm_out(const_cast<Tensor&>(C), A, Bop);
-  }
-}
-
-// Two independent products in ONE tmdnet_gemm_f32 launch when both fit the grouped kernel (the layer's
-// [q|k|v]^T and vec_proj^T input gradients: 8 launches fewer per C2 force pass); else two gemm_into
-void gemm2_into(const Tensor& A1, const Tensor& B1, bool tb1, const Tensor& C1, bool beta1, const Tensor& A2,
-                const Tensor& B2, bool tb2, const Tensor& C2, bool beta2) {
-  auto ok = [](const Tensor& A, const Tensor& B, const Tensor& C) {
-    return A.scalar_type() == at::kFloat && A.size(0) > 0 && A.size(0) <= 16384 && A.stride(1) == 1 &&
-           B.stride(1) == 1 && C.stride(1) == 1;
-  };
-  if (ok(A1, B1, C1) && ok(A2, B2, C2)) {
-    int dims[16];
-    const void* ptrs[8];
-    const Tensor* As[2] = {&A1, &A2};
-    const Tensor* Bs[2] = {&B1, &B2};
-    const Tensor* Cs[2] = {&C1, &C2};
-    const bool tb[2] = {tb1, tb2}, be[2] = {beta1, beta2};
-    for (int i = 0; i < 2; ++i) {
-      const Tensor &A = *As[i], &B = *Bs[i], &C = *Cs[i];
-      const int d[8] = {static_cast<int>(A.size(0)), static_cast<int>(C.size(1)), static_cast<int>(A.size(1)),
-                        static_cast<int>(A.stride(0)), static_cast<int>(B.stride(0)), static_cast<int>(C.stride(0)),
-                        int(tb[i]), int(be[i])};
-      for (int j = 0; j < 8; ++j) dims[8 * i + j] = d[j];
-      ptrs[4 * i] = A.data_ptr();
-      ptrs[4 * i + 1] = B.data_ptr();
-      ptrs[4 * i + 2] = nullptr;
-      ptrs[4 * i + 3] = C.data_ptr();
-    }
-    const int rc = tmdnet_gemm_f32(2, dims, ptrs, stream_of(A1));
-    if (rc != TMDNET_UNSUPPORTED) {
-      check(rc, "tmdnet_gemm_f32");
-      return;
-    }
-  }
-  gemm_into(A1, B1, tb1, Tensor(), C1, beta1);
-  gemm_into(A2, B2, tb2, Tensor(), C2, beta2);
 }
 
 // out = A W^T (+ bias) for the dk/dv projection (tmdnet_proj_f32 on the exact bf16 split; library otherwise)
@@ -1427,7 +1427,7 @@ variable_list stack_backward_dr(const StackActs& A, Tensor gX, Tensor gV, const 
     g_xa_pre = Tensor();
     if (!g_xa.defined()) {
       g_xa = at::empty({N, H}, o);
-      gemm_into(g_o[l], p[9], false, Tensor(), g_xa, false);
+      gemm_group_into({{g_o[l], p[9], false, Tensor(), g_xa, false}});
     }
     const bool hv = A.vec[l].defined();
     Tensor g_vec_in = hv ? at::empty({N, 3, H}, o) : Tensor();
@@ -1459,10 +1459,10 @@ variable_list stack_backward_dr(const StackActs& A, Tensor gX, Tensor gV, const 
           "tmdnet_et_message_bwd");
     Tensor g_xn = at::empty({N, H}, o);
     if (hv)
-      gemm2_into(g_qkv, A.pk->qkv_w[l], false, g_xn, false, g_vecp[l].view({3 * N, 3 * H}), p[8], false,
-                 g_vec_in.view({3 * N, H}), true);
+      gemm_group_into({{g_qkv, A.pk->qkv_w[l], false, Tensor(), g_xn, false},
+                       {g_vecp[l].view({3 * N, 3 * H}), p[8], false, Tensor(), g_vec_in.view({3 * N, H}), true}});
     else
-      gemm_into(g_qkv, A.pk->qkv_w[l], false, Tensor(), g_xn, false);
+      gemm_group_into({{g_qkv, A.pk->qkv_w[l], false, Tensor(), g_xn, false}});
     const bool prev = l > 0;
     Tensor g_x;
     if (nf && prev) {
@@ -1626,10 +1626,10 @@ std::pair<Tensor, Tensor> stack_forward(const Tensor& x_in, const Tensor& f_in, 
       if (nf) {  // LayerNorm + [q|k|v] + vec_proj in one launch
         ln_mix(x, p[0], p[1], A->pk->qkv_w[l], A->pk->qkv_b[l], vec, p[8], qkv, &vecp, &xn, &mean, &rstd);
       } else {
-        gemm_into(xn, A->pk->qkv_w[l], true, A->pk->qkv_b[l], qkv, false);
+        gemm_group_into({{xn, A->pk->qkv_w[l], true, A->pk->qkv_b[l], qkv, false}});
         if (vec.defined()) {
           vecp = at::empty({N, 3, 3 * H}, o);
-          gemm_into(vec.view({3 * N, H}), p[8], true, Tensor(), vecp.view({3 * N, 3 * H}), false);
+          gemm_group_into({{vec.view({3 * N, H}), p[8], true, Tensor(), vecp.view({3 * N, 3 * H}), false}});
         }
       }
       Tensor pkv, pk, pv;
@@ -1656,7 +1656,7 @@ std::pair<Tensor, Tensor> stack_forward(const Tensor& x_in, const Tensor& f_in, 
       if (nf && l + 1 < L) {  // o_proj + the epilogue in one launch (the next LayerNorm: its mix)
         oproj_epi(xa, p[9], p[10], x, vec, vecp, veca, oo, &xo, &vo);
       } else {
-        gemm_into(xa, p[9], true, p[10], oo, false);
+        gemm_group_into({{xa, p[9], true, p[10], oo, false}});
       }
       A->x.push_back(x); A->vec.push_back(vec); A->xn.push_back(xn); A->mean.push_back(mean);
       A->rstd.push_back(rstd); A->qkv.push_back(qkv); A->vecp.push_back(vecp); A->xa.push_back(xa);
@@ -1870,10 +1870,10 @@ std::pair<Tensor, Tensor> stack_forward_fused(const Tensor& x_in, const Tensor& 
     if (nf) {
       ln_mix(x, p[0], p[1], F->qkv_w[l], F->qkv_b[l], vec, p[8], qkv, &vecp, &xn, &mean, &rstd);
     } else {
-      gemm_into(xn, F->qkv_w[l], true, F->qkv_b[l], qkv, false);
+      gemm_group_into({{xn, F->qkv_w[l], true, F->qkv_b[l], qkv, false}});
       if (vec.defined()) {
         vecp = at::empty({N, 3, 3 * H}, o);
-        gemm_into(vec.view({3 * N, H}), p[8], true, Tensor(), vecp.view({3 * N, 3 * H}), false);
+        gemm_group_into({{vec.view({3 * N, H}), p[8], true, Tensor(), vecp.view({3 * N, 3 * H}), false}});
       }
     }
     Tensor xa = at::empty({N, H}, o), veca = at::empty({N, 3, H}, o);
@@ -1889,7 +1889,7 @@ std::pair<Tensor, Tensor> stack_forward_fused(const Tensor& x_in, const Tensor& 
     if (nf && l + 1 < L)
       oproj_epi(xa, p[9], p[10], x, vec, vecp, veca, oo, &xo, &vo);
     else
-      gemm_into(xa, p[9], true, p[10], oo, false);
+      gemm_group_into({{xa, p[9], true, p[10], oo, false}});
     A->x.push_back(x); A->vec.push_back(vec); A->xn.push_back(xn); A->mean.push_back(mean);
     A->rstd.push_back(rstd); A->qkv.push_back(qkv); A->vecp.push_back(vecp); A->xa.push_back(xa);
     A->o.push_back(oo);
@@ -1946,7 +1946,7 @@ variable_list stack_backward_fused(const StackActs& A, const FusedAux& F, Tensor
     g_xa_pre = Tensor();
     if (!g_xa.defined()) {
       g_xa = at::empty({N, H}, o);
-      gemm_into(g_o[l], p[9], false, Tensor(), g_xa, false);
+      gemm_group_into({{g_o[l], p[9], false, Tensor(), g_xa, false}});
     }
     const bool hv = A.vec[l].defined();
     Tensor g_vec_in = hv ? at::empty({N, 3, H}, o) : Tensor();
@@ -1964,10 +1964,10 @@ variable_list stack_backward_fused(const StackActs& A, const FusedAux& F, Tensor
           "tmdnet_et_fused_bwd_f32");
     Tensor g_xn = at::empty({N, H}, o);
     if (hv)
-      gemm2_into(g_qkv, F.qkv_w[l], false, g_xn, false, g_vecp[l].view({3 * N, 3 * H}), p[8], false,
-                 g_vec_in.view({3 * N, H}), true);
+      gemm_group_into({{g_qkv, F.qkv_w[l], false, Tensor(), g_xn, false},
+                       {g_vecp[l].view({3 * N, 3 * H}), p[8], false, Tensor(), g_vec_in.view({3 * N, H}), true}});
     else
-      gemm_into(g_qkv, F.qkv_w[l], false, Tensor(), g_xn, false);
+      gemm_group_into({{g_qkv, F.qkv_w[l], false, Tensor(), g_xn, false}});
     const bool prev = l > 0;
     Tensor g_x;
     if (nf && prev) {
@@ -2103,14 +2103,14 @@ std::tuple<Tensor, Tensor> et_energy_forces(
             "tmdnet_nbr_fused_fwd_f32");
     } else {
       W = at::empty({E, H}, o);
-      gemm_into(f, val(nb_dist_w_), true, val(nb_dist_b_), W, false);
+      gemm_group_into({{f, val(nb_dist_w_), true, val(nb_dist_b_), W, false}});
       check(tmdnet_nbr_embed_fwd(dt, static_cast<int>(N), static_cast<int>(H), ptr<int32_t>(row_ptr),
                                  ptr<int32_t>(src), static_cast<int>(E), ptr(xe), static_cast<int>(H), ptr(W),
                                  static_cast<int>(H), ptr(C), cb + H, static_cast<int>(2 * H), ptr(x), cb, st),
             "tmdnet_nbr_embed_fwd");
     }
     x1 = at::empty({N, H}, o);
-    gemm_into(cat, val(nb_comb_w_), true, val(nb_comb_b_), x1, false);
+    gemm_group_into({{cat, val(nb_comb_w_), true, val(nb_comb_b_), x1, false}});
   }
   // the layer stack
   StackCfg c{heads, rbf_type, cl, cu, has_dk, has_dv, out_norm, acts};
@@ -2172,7 +2172,7 @@ std::tuple<Tensor, Tensor> et_energy_forces(
   Tensor gf, gC_nb;
   if (nb_fused) {  // dr mode: g_C and g_r per edge, added to the stack's (no E x H / E x R gradient rows)
     Tensor g_cat = at::empty({N, 2 * H}, o);
-    gemm_into(gs[0], val(nb_comb_w_), false, Tensor(), g_cat, false);
+    gemm_group_into({{gs[0], val(nb_comb_w_), false, Tensor(), g_cat, false}});
     const float* gcb = static_cast<const float*>(g_cat.data_ptr());
     check(tmdnet_nbr_fused_bwd_f32(static_cast<int>(N), static_cast<int>(H), static_cast<int>(R), ptr<int32_t>(row_ptr),
                                    ptr<int32_t>(src), static_cast<int>(E), ptr(xe), static_cast<int>(H), ptr(C),
@@ -2182,7 +2182,7 @@ std::tuple<Tensor, Tensor> et_energy_forces(
           "tmdnet_nbr_fused_bwd_f32");
   } else if (nb) {
     Tensor g_cat = at::empty({N, 2 * H}, o);
-    gemm_into(gs[0], val(nb_comb_w_), false, Tensor(), g_cat, false);
+    gemm_group_into({{gs[0], val(nb_comb_w_), false, Tensor(), g_cat, false}});
     Tensor gW = at::empty({E, H}, o);
     gC_nb = at::empty({E}, o);
     const float* gcb = static_cast<const float*>(g_cat.data_ptr());
@@ -2191,7 +2191,7 @@ std::tuple<Tensor, Tensor> et_energy_forces(
                                gcb + H, static_cast<int>(2 * H), nullptr, ptr(gW), ptr(gC_nb), st),
           "tmdnet_nbr_embed_bwd");
     gf = at::empty({E, R}, o);
-    gemm_into(gW, val(nb_dist_w_), false, Tensor(), gf, false);
+    gemm_group_into({{gW, val(nb_dist_w_), false, Tensor(), gf, false}});
   }
   Tensor g_r = at::empty({E}, o), g_dl = at::empty({E, 3}, o);
   check(tmdnet_edge_geom_bwd_multi(dt, static_cast<int>(E), static_cast<int>(R), static_cast<int>(rbf_type),

@@ -10,6 +10,7 @@ import ctypes
 import math
 import os
 import weakref
+from collections import namedtuple
 
 import torch
 import torch.nn.functional as F
@@ -1434,38 +1435,14 @@ def fused_act(act, x, scale=None):
     return y if scale is None else y * scale.view(-1, 1)
 
 
-# ----------------------------------------------------------------------------- small grouped GEMM
+# ----------------------------------------------------------------------------- dense GEMM
+# C = beta C + A op(B) + bias on one of three back ends: the grouped split-K kernel (tmdnet_gemm_ex_f32, up to
+# 4 problems a launch, up to GEMM_MAX_ROWS rows), the x3 kernel above that (tmdnet_gemm_x3_ex_f32: bf16 MFMA on
+# an exact three-piece split, fp32 accuracy), the library.  gemm_group routes plain problems, gemm_ex_launch the ones
+# with an epilogue (no library form); each kernel's envelope is stated once, in *_shape_ok / *_ok below.
 GEMM_UNSUPPORTED = 2
 GEMM_MAX_ROWS = 16384  # the grouped split-K kernel's envelope; above it the x3 GEMM (gemm_x3) takes the rows
-
-
-def gemm_launch(problems):
-    """``tmdnet_gemm_f32``: up to 4 problems (A, B, trans_b, bias, C, beta) in one launch,
-    C = beta C + A op(B) + bias.  Returns False (nothing launched) when a problem is outside the
-    kernel's envelope (non-fp32, empty, K % 16, alignment); the caller then uses the library GEMM."""
-    if any(A.dtype != torch.float32 or not 0 < A.shape[0] <= GEMM_MAX_ROWS or A.shape[1] == 0 or C.shape[1] == 0
-           for A, _, _, _, C, _ in problems):
-        return False
-    lib = nat.load()
-    n = len(problems)
-    dims = (ctypes.c_int * (8 * n))()
-    ptrs = (ctypes.c_void_p * (4 * n))()
-    for i, (A, B, tb, bias, C, beta) in enumerate(problems):
-        if A.stride(1) != 1 or B.stride(1) != 1 or C.stride(1) != 1:
-            return False
-        dims[8 * i:8 * i + 8] = [A.shape[0], C.shape[1], A.shape[1], A.stride(0), B.stride(0), C.stride(0),
-                                 int(tb), int(beta)]
-        ptrs[4 * i:4 * i + 4] = [A.data_ptr(), B.data_ptr(), None if bias is None else bias.data_ptr(),
-                                 C.data_ptr()]
-    rc = lib.tmdnet_gemm_f32(n, dims, ptrs, nat.stream(problems[0][0].device))
-    if rc == GEMM_UNSUPPORTED:
-        return False
-    nat.check(rc, "tmdnet_gemm_f32")
-    return True
-
-
-# above GEMM_MAX_ROWS (C5-size systems) fp32 GEMMs run on tmdnet_gemm_x3_f32 (bf16 MFMA, exact three-piece
-# split, fp32 accuracy); TMDNET_GEMM_BIG=lib keeps the library GEMM there (A/B switch)
+# TMDNET_GEMM_BIG=lib keeps the library GEMM above GEMM_MAX_ROWS (A/B switch)
 GEMM_BIG = os.environ.get("TMDNET_GEMM_BIG", "x3")
 # where the weight's bf16 pieces come from: "launch" = a split launch per call (tmdnet_proj_split_f32 /
 # tmdnet_split_t_f32, ~5 us each; nothing cached, so in-place weight updates are always seen), "kernel" = split
@@ -1475,78 +1452,149 @@ GEMM_BIG = os.environ.get("TMDNET_GEMM_BIG", "x3")
 X3_WSPLIT = os.environ.get("TMDNET_X3_WSPLIT", "launch")
 
 
+# One problem C = beta C + A op(B) + bias, op(B) = B^T for a [N][K] Linear weight (trans_b), B for a [K][N] right
+# operand; a plain 6-tuple p is Gemm(*p).  The epilogue fields (kernels only): the sum is stored to pre (the
+# pre-activation a backward needs), then SiLU (act = 1), times rscale[:, None], times silu'(dpre), then C.
+Gemm = namedtuple("Gemm", "A B trans_b bias C beta act pre rscale dpre", defaults=(0, None, None, None))
+
+
+def grouped_shape_ok(M, N, K):
+    """Shapes tmdnet_gemm_ex_f32 takes (K in 16-wide blocks split over the waves)."""
+    return 0 < M <= GEMM_MAX_ROWS and N > 0 and K > 0 and K % 16 == 0
+
+
+def x3_shape_ok(M, N, K):
+    """Shapes tmdnet_gemm_x3_ex_f32 takes (32-wide bf16 MFMA K steps, 16-column output tiles)."""
+    return GEMM_BIG == "x3" and M > 0 and K % 32 == 0 and N % 16 == 0
+
+
 def _al16(*ts):
     return all(t is None or (t.data_ptr() % 16 == 0) for t in ts)
 
 
+def _rows16(t):
+    """A 2-D operand a kernel accesses 16 bytes at a time: aligned base, row stride a multiple of 4 floats."""
+    return t is None or (t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0)
+
+
+def _operands_ok(p):
+    """What both kernels need of a Gemm's operands: fp32 on the device, unit column strides, dense bias and row
+    scale, pre / dpre laid out like C with one row stride between them."""
+    A, B, C, pre, dpre = p.A, p.B, p.C, p.pre, p.dpre
+    return (A.is_cuda and B.is_cuda and C.is_cuda
+            and A.dtype == torch.float32 and B.dtype == torch.float32 and C.dtype == torch.float32
+            and A.stride(1) == 1 and B.stride(1) == 1 and C.stride(1) == 1
+            and (p.bias is None or p.bias.is_contiguous())
+            and (p.rscale is None or (p.rscale.is_contiguous() and p.rscale.dtype == torch.float32))
+            and (pre is None or (pre.shape == C.shape and pre.stride(1) == 1))
+            and (dpre is None or (dpre.shape == C.shape and dpre.stride(1) == 1))
+            and (pre is None or dpre is None or pre.stride(0) == dpre.stride(0)))
+
+
+def grouped_ok(p):
+    """The grouped kernel's envelope (gemm.hip gemm_run): 16-byte loads of A's rows, and of B's [N][K] rows."""
+    return grouped_shape_ok(p.A.shape[0], p.C.shape[1], p.A.shape[1]) and _operands_ok(p) \
+        and _rows16(p.A) and (not p.trans_b or _rows16(p.B))
+
+
+def x3_ok(p):
+    """The x3 kernel's envelope (gemm.hip tmdnet_gemm_x3_ex_f32 and the weight splits): 16 bytes throughout."""
+    return x3_shape_ok(p.A.shape[0], p.C.shape[1], p.A.shape[1]) and _operands_ok(p) and _rows16(p.A) \
+        and _rows16(p.B) and _rows16(p.C) and _rows16(p.pre) and _rows16(p.dpre) and _al16(p.bias)
+
+
+def gemm_launch(problems):
+    """Up to 4 Gemm (or 6-tuple) problems, plain or with an epilogue, in ONE ``tmdnet_gemm_ex_f32`` launch.
+    Returns False, nothing launched, when any is outside the kernel's envelope."""
+    ps = [Gemm(*p) for p in problems]
+    if not 0 < len(ps) <= 4 or not all(grouped_ok(p) for p in ps):
+        return False
+    n = len(ps)
+    dims = (ctypes.c_int * (10 * n))()
+    ptrs = (ctypes.c_void_p * (7 * n))()
+    for i, p in enumerate(ps):
+        x = p.pre if p.pre is not None else p.dpre
+        dims[10 * i:10 * i + 10] = [p.A.shape[0], p.C.shape[1], p.A.shape[1], p.A.stride(0), p.B.stride(0),
+                                    p.C.stride(0), int(bool(p.trans_b)), int(bool(p.beta)), int(p.act),
+                                    0 if x is None else x.stride(0)]
+        ptrs[7 * i:7 * i + 7] = [None if t is None else t.data_ptr()
+                                 for t in (p.A, p.B, p.bias, p.C, p.pre, p.rscale, p.dpre)]
+    rc = nat.load().tmdnet_gemm_ex_f32(n, dims, ptrs, nat.stream(ps[0].A.device))
+    if rc == GEMM_UNSUPPORTED:
+        return False
+    nat.check(rc, "tmdnet_gemm_ex_f32")
+    return True
+
+
 def gemm_x3(A, B, tb, bias, C, beta, act=0, pre=None, rscale=None, dpre=None):
-    """``C = beta C + A op(B) + bias`` on ``tmdnet_gemm_x3_f32`` for large row counts: op(B) = B^T for a
-    [N][K] Linear weight (split once per call, tmdnet_proj_split_f32), B for a [K][N] right operand
-    (tmdnet_split_t_f32).  ``act`` / ``pre`` / ``rscale`` / ``dpre``: tmdnet_gemm_ex_f32's epilogue
-    (tmdnet_gemm_x3_ex_f32).  Returns False (nothing launched) outside its envelope (non-fp32, K % 32,
-    N % 16, strides / alignment); the caller then uses the library GEMM."""
+    """One Gemm on ``tmdnet_gemm_x3_ex_f32`` for large row counts: B's three bf16 pieces split once per call
+    (tmdnet_proj_split_f32 for a [N][K] weight, tmdnet_split_t_f32 for a [K][N] right operand).  Returns False
+    (nothing launched) outside its envelope (x3_ok)."""
+    if not x3_ok(Gemm(A, B, tb, bias, C, beta, act, pre, rscale, dpre)):
+        return False
     M, K = A.shape
     N = C.shape[1]
     x = pre if pre is not None else dpre
-    if not (GEMM_BIG == "x3" and A.is_cuda and A.dtype == torch.float32 and B.dtype == torch.float32
-            and C.dtype == torch.float32 and M > 0 and K % 32 == 0 and N % 16 == 0 and A.stride(1) == 1
-            and B.stride(1) == 1 and C.stride(1) == 1 and A.stride(0) % 4 == 0 and C.stride(0) % 4 == 0
-            and B.stride(0) % 4 == 0 and (bias is None or bias.is_contiguous()) and _al16(A, B, C, bias, pre, dpre)
-            and (x is None or (x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.shape == C.shape))
-            and (pre is None or dpre is None or pre.stride(0) == dpre.stride(0))
-            and (rscale is None or (rscale.is_contiguous() and rscale.dtype == torch.float32))):
-        return False
     lib = nat.load()
     st = nat.stream(A.device)
-    if X3_WSPLIT == "kernel" and B.data_ptr() % 16 == 0:
+    epi = (int(bool(beta)), int(act), nat.ptr(pre), nat.ptr(rscale), nat.ptr(dpre), 0 if x is None else x.stride(0))
+    if X3_WSPLIT == "kernel":
         # the weight split inside the GEMM while it is staged in LDS (no split launch, nothing cached)
         rc = lib.tmdnet_gemm_x3w_f32(M, N, K, A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), int(bool(tb)),
-                                     None if bias is None else bias.data_ptr(), C.data_ptr(), C.stride(0),
-                                     int(bool(beta)), int(act), nat.ptr(pre), nat.ptr(rscale), nat.ptr(dpre),
-                                     0 if x is None else x.stride(0), st)
+                                     nat.ptr(bias), C.data_ptr(), C.stride(0), *epi, st)
         if rc != GEMM_UNSUPPORTED:
             nat.check(rc, "tmdnet_gemm_x3w_f32")
             return True
     bp = torch.empty((3, N, K), dtype=torch.int16, device=A.device)
-    if tb:
-        rc = lib.tmdnet_proj_split_f32(N, K, B.data_ptr(), B.stride(0), bp.data_ptr(), st)
-    else:
-        rc = lib.tmdnet_split_t_f32(N, K, B.data_ptr(), B.stride(0), bp.data_ptr(), st)
+    split = lib.tmdnet_proj_split_f32 if tb else lib.tmdnet_split_t_f32
+    rc = split(N, K, B.data_ptr(), B.stride(0), bp.data_ptr(), st)
     if rc == GEMM_UNSUPPORTED:
         return False
     nat.check(rc, "tmdnet_split")
-    rc = lib.tmdnet_gemm_x3_ex_f32(M, N, K, A.data_ptr(), A.stride(0), bp.data_ptr(),
-                                   None if bias is None else bias.data_ptr(), C.data_ptr(), C.stride(0),
-                                   int(bool(beta)), int(act), nat.ptr(pre), nat.ptr(rscale), nat.ptr(dpre),
-                                   0 if x is None else x.stride(0), st)
+    rc = lib.tmdnet_gemm_x3_ex_f32(M, N, K, A.data_ptr(), A.stride(0), bp.data_ptr(), nat.ptr(bias), C.data_ptr(),
+                                   C.stride(0), *epi, st)
     if rc == GEMM_UNSUPPORTED:
         return False
     nat.check(rc, "tmdnet_gemm_x3_ex_f32")
     return True
 
 
+def gemm_lib(p):
+    """One plain Gemm on the library (fp64 parity runs, CPU operands, shapes outside both kernels)."""
+    Bop = p.B.t() if p.trans_b else p.B
+    if p.beta:
+        p.C.addmm_(p.A, Bop)
+        if p.bias is not None:
+            p.C.add_(p.bias)
+    elif p.bias is not None:
+        torch.addmm(p.bias, p.A, Bop, out=p.C)
+    else:
+        torch.mm(p.A, Bop, out=p.C)
+    return p.C
+
+
 def gemm_group(problems):
-    """The node feature-mix GEMMs of one step, grouped into one launch when the kernel supports
-    them (fp32, up to GEMM_MAX_ROWS rows); large systems one tmdnet_gemm_x3_f32 launch each; otherwise
-    the library GEMM (fp64 parity runs)."""
-    if gemm_launch(problems):
+    """The router of plain problems (Gemm records or 6-tuples, at most 4 to share a launch): the whole group in
+    one grouped launch when every problem is inside that kernel's envelope; otherwise per problem the x3 kernel
+    above GEMM_MAX_ROWS rows, a grouped launch of its own at or below (a group with rows on both sides), and
+    the library for what neither takes."""
+    ps = [Gemm(*p) for p in problems]
+    if gemm_launch(ps):
         return
-    mixed = len(problems) > 1
-    for A, B, tb, bias, C, beta in problems:
-        if A.shape[0] > GEMM_MAX_ROWS:
-            if gemm_x3(A, B, tb, bias, C, beta):
+    for p in ps:
+        if p.A.shape[0] > GEMM_MAX_ROWS:
+            if gemm_x3(*p[:6]):
                 continue
-        elif mixed and gemm_launch([(A, B, tb, bias, C, beta)]):  # (a group with rows on both sides)
+        elif len(ps) > 1 and gemm_launch([p]):
             continue
-        Bop = B.t() if tb else B
-        if beta:
-            C.addmm_(A, Bop)
-            if bias is not None:
-                C.add_(bias)
-        elif bias is not None:
-            torch.addmm(bias, A, Bop, out=C)
-        else:
-            torch.mm(A, Bop, out=C)
+        gemm_lib(p)
+
+
+def gemm_ex_launch(p):
+    """One Gemm with an epilogue (act / pre / rscale / dpre; no library form): the x3 kernel above GEMM_MAX_ROWS
+    rows, the grouped kernel at or below.  Returns False, nothing launched, outside that kernel's envelope."""
+    p = Gemm(*p)
+    return gemm_x3(*p) if p.A.shape[0] > GEMM_MAX_ROWS else gemm_launch([p])
 
 
 # ET dk/dv projection on the bf16 MFMA with an exact three-piece split (fp32 accuracy); TMDNET_PROJ=lib
@@ -1590,9 +1638,7 @@ def proj(A, W, bias=None, out=None, wp=None, row0=0):
             if rc != GEMM_UNSUPPORTED:
                 nat.check(rc, "tmdnet_proj_f32")
                 return out
-    if bias is not None:
-        return torch.addmm(bias, A, W.t(), out=out)
-    return torch.mm(A, W.t(), out=out)
+    return gemm_lib(Gemm(A, W, True, bias, out, False))
 
 
 def wgrad_tn(problems):
@@ -2552,12 +2598,10 @@ class _Linear(Function):
     def forward(ctx, x, w, b):
         ctx.save_for_backward(x, w)
         ctx.has_b = b is not None
-        if x.dim() == 2 and x.is_cuda and x.dtype == torch.float32:  # hand-written MFMA GEMM (tmdnet_gemm_f32)
+        if x.dim() == 2:  # the hand-written GEMMs, or the library (gemm_group)
             y = torch.empty((x.shape[0], w.shape[0]), dtype=x.dtype, device=x.device)
-            if gemm_launch([(x, w, True, b, y, False)]):
-                return y
-            if x.shape[0] > GEMM_MAX_ROWS and gemm_x3(x, w, True, b, y, False):
-                return y
+            gemm_group([(x, w, True, b, y, False)])
+            return y
         return F.linear(x, w, b)
 
     @staticmethod
@@ -2606,9 +2650,7 @@ class _LinearBwd(Function):
         if need[0]:
             gy = gy.contiguous()
             gx = torch.empty((gy.shape[0], w.shape[1]), dtype=gy.dtype, device=gy.device)
-            if not (gy.is_cuda and (gemm_launch([(gy, w, False, None, gx, False)])
-                                    or (gy.shape[0] > GEMM_MAX_ROWS and gemm_x3(gy, w, False, None, gx, False)))):
-                torch.mm(gy, w, out=gx)
+            gemm_group([(gy, w, False, None, gx, False)])
         gw, gb = _linear_wgrad(gy, x, need[1], need[2]) if (need[1] or need[2]) else (None, None)
         ctx.save_for_backward(gy, x, w)
         return gx, gw, gb
@@ -2661,60 +2703,6 @@ def linear(x, w, b=None):
 
 
 # ----------------------------------------------------------------------------- Linear + SiLU stacks
-def gemm_ex_launch(problems):
-    """``tmdnet_gemm_ex_f32``: up to 4 problems, dicts with A, B, C and optional trans_b (default True),
-    bias, beta, act (0/1), pre, rscale, dpre (pre / dpre share a row stride).  Returns False when
-    outside the kernel's envelope (nothing launched)."""
-    if not problems or len(problems) > 4:
-        return False
-    if any(p["A"].shape[0] > GEMM_MAX_ROWS for p in problems):
-        # large systems: one tmdnet_gemm_x3_ex_f32 launch per problem (same epilogue), all or nothing
-        ok = [_x3_ex_ok(p) for p in problems]
-        if not all(ok):
-            return False
-        for p in problems:
-            if not gemm_x3(p["A"], p["B"], p.get("trans_b", True), p.get("bias"), p["C"], p.get("beta"),
-                           act=int(p.get("act", 0)), pre=p.get("pre"), rscale=p.get("rscale"), dpre=p.get("dpre")):
-                raise RuntimeError("gemm_ex_launch: tmdnet_gemm_x3_ex_f32 refused a checked problem")
-        return True
-    for p in problems:
-        A, C = p["A"], p["C"]
-        if (A.dtype != torch.float32 or not A.is_cuda or not 0 < A.shape[0] <= GEMM_MAX_ROWS or A.shape[1] == 0
-                or C.shape[1] == 0 or A.stride(1) != 1 or p["B"].stride(1) != 1 or C.stride(1) != 1):
-            return False
-    lib = nat.load()
-    n = len(problems)
-    dims = (ctypes.c_int * (10 * n))()
-    ptrs = (ctypes.c_void_p * (7 * n))()
-    for i, p in enumerate(problems):
-        A, B, C = p["A"], p["B"], p["C"]
-        x = p.get("pre") if p.get("pre") is not None else p.get("dpre")
-        if x is not None and (x.stride(1) != 1 or x.shape != C.shape):
-            return False
-        dims[10 * i:10 * i + 10] = [A.shape[0], C.shape[1], A.shape[1], A.stride(0), B.stride(0), C.stride(0),
-                                    int(p.get("trans_b", True)), int(bool(p.get("beta"))), int(p.get("act", 0)),
-                                    0 if x is None else x.stride(0)]
-        ptrs[7 * i:7 * i + 7] = [A.data_ptr(), B.data_ptr()] + [
-            None if p.get(k) is None else p[k].data_ptr() for k in ("bias", "C", "pre", "rscale", "dpre")]
-    rc = lib.tmdnet_gemm_ex_f32(n, dims, ptrs, nat.stream(problems[0]["A"].device))
-    if rc == GEMM_UNSUPPORTED:
-        return False
-    nat.check(rc, "tmdnet_gemm_ex_f32")
-    return True
-
-
-def _x3_ex_ok(p):
-    """Whether gemm_x3 takes problem p (the x3 kernel's envelope, checked before anything launches)."""
-    A, B, C = p["A"], p["B"], p["C"]
-    bias, x = p.get("bias"), (p.get("pre") if p.get("pre") is not None else p.get("dpre"))
-    return (GEMM_BIG == "x3" and A.is_cuda and all(t.dtype == torch.float32 for t in (A, B, C))
-            and A.shape[0] > 0 and A.shape[1] % 32 == 0 and C.shape[1] % 16 == 0
-            and A.stride(1) == 1 and B.stride(1) == 1 and C.stride(1) == 1
-            and A.stride(0) % 4 == 0 and B.stride(0) % 4 == 0 and C.stride(0) % 4 == 0
-            and (bias is None or bias.is_contiguous()) and _al16(A, B, C, bias, p.get("pre"), p.get("dpre"))
-            and (x is None or (x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.shape == C.shape)))
-
-
 def _mlp_composite(x, scale, *wb):
     """Differentiable restatement: silu(Linear) layers, the last one times scale[:, None]."""
     L = len(wb) // 2
@@ -2741,9 +2729,8 @@ class _MLPAct(Function):
         for i in range(L):
             pre = torch.empty((x.shape[0], ws[i].shape[0]), **o)
             y = torch.empty_like(pre)
-            ok = gemm_ex_launch([{"A": h, "B": ws[i], "bias": bs[i], "C": y, "pre": pre, "act": 1,
-                                  "rscale": scale if i == L - 1 else None}])
-            if not ok:
+            if not gemm_ex_launch(Gemm(h, ws[i], True, bs[i], y, False, act=1, pre=pre,
+                                rscale=scale if i == L - 1 else None)):
                 raise RuntimeError("mlp_act: shape outside tmdnet_gemm_ex_f32's envelope")
             pres.append(pre)
             hs.append(h)
@@ -2788,13 +2775,13 @@ class _MLPActBwd(Function):
             if i > 0:  # the lower layer's pre-activation gradient: (g_pre_i W_i) * silu'(pre_{i-1})
                 g = torch.empty_like(pres[i - 1])
                 ups[i - 1] = torch.empty_like(pres[i - 1])
-                gemm_ex_launch([{"A": gpres[i], "B": ws[i], "trans_b": False, "C": g, "dpre": pres[i - 1],
-                                 "pre": ups[i - 1]}]) or _raise("mlp_act backward: GEMM envelope")
+                if not gemm_ex_launch(Gemm(gpres[i], ws[i], False, None, g, False, pre=ups[i - 1], dpre=pres[i - 1])):
+                    raise RuntimeError("mlp_act backward: GEMM envelope")
                 gpres[i - 1] = g
             elif need[0]:
                 gx = torch.empty_like(x)
-                gemm_ex_launch([{"A": gpres[0], "B": ws[0], "trans_b": False, "C": gx}]) or \
-                    _raise("mlp_act backward: GEMM envelope")
+                if not gemm_ex_launch(Gemm(gpres[0], ws[0], False, None, gx, False)):
+                    raise RuntimeError("mlp_act backward: GEMM envelope")
         gw, gb = [None] * L, [None] * L
         tn = []
         for i in range(L):
@@ -2825,10 +2812,6 @@ class _MLPActBwd(Function):
         d = _double_backward(_mlp_composite, [x, scale] + wb, [gy], list(ggs))
         # (need, gy, x, scale, *ws, *bs, *pres, *hmid): pres / hmid are functions of the others
         return (None, d[0], d[1], d[2], *d[3:3 + 2 * L]) + (None,) * (2 * L - 1)
-
-
-def _raise(msg):
-    raise RuntimeError(msg)
 
 
 def _mlp_second_order(ctx, sv, ggs):
@@ -2927,20 +2910,22 @@ def mlp_act(x, weights, biases, act, scale=None):
     """``act(... act(x W_0^T + b_0) ...) * scale[:, None]`` for nn.Linear weights / biases: the hand
     fused path for SiLU on fp32 CUDA rows within the GEMM envelope, else Linear + fused_act per layer."""
     L = len(weights)
-    # (above GEMM_MAX_ROWS rows every GEMM runs on tmdnet_gemm_x3_ex_f32, which needs K % 32 in both directions)
-    big = x.dim() == 2 and x.shape[0] > GEMM_MAX_ROWS
-    mod = 32 if big else 16
     ok = (MLP_ACT and isinstance(act, torch.nn.SiLU) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
-          and 0 < x.shape[0] and (not big or GEMM_BIG == "x3") and all(b is not None for b in biases)
-          and all(w.shape[1] % mod == 0 for w in weights) and all(w.shape[0] % mod == 0 for w in weights))
+          and all(b is not None for b in biases))
+    if ok:
+        # every layer's GEMM in both directions (forward x W^T: N, K = W's shape; the backward's g W: K, N) on the
+        # kernel the row count selects
+        M = x.shape[0]
+        shape_ok = x3_shape_ok if M > GEMM_MAX_ROWS else grouped_shape_ok
+        ok = all(shape_ok(M, w.shape[0], w.shape[1]) and shape_ok(M, w.shape[1], w.shape[0]) for w in weights)
     if ok:
         # tmdnet_gemm_ex_f32 also needs 16-byte aligned operands (a contiguous view with a storage offset
         # may not be): realign x by a copy, take the composite for misaligned weights
         x = x.contiguous()
-        if x.data_ptr() % 16:
+        if not _al16(x):
             x = x.clone()
-        ok = all(w.is_contiguous() and w.data_ptr() % 16 == 0 for w in weights) and \
-            all(b.data_ptr() % 16 == 0 for b in biases) and (scale is None or scale.contiguous().data_ptr() % 16 == 0)
+        ok = all(t.is_contiguous() for t in (*weights, *biases)) and \
+            _al16(*weights, *biases, None if scale is None else scale.contiguous())
     if not ok:
         for i in range(L):
             x = fused_act(act, linear(x, weights[i], biases[i]), scale if i == L - 1 else None)

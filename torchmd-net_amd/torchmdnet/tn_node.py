@@ -289,12 +289,9 @@ class _Mix3(Function):
     def forward(ctx, c, w0, w1, w2):
         c = c.contiguous()
         out = torch.empty((9, c.shape[1], w0.shape[0]), dtype=c.dtype, device=c.device)
-        probs = [(src, w, True, None, dst, False) for src, w, dst in zip(_blocks(c), (w0, w1, w2), _blocks(out))]
-        if c.is_cuda:  # one hand-written launch (x3 GEMMs above GEMM_MAX_ROWS rows; the library for fp64)
-            kernels.gemm_group(probs)
-        else:
-            for src, w, _, _, dst, _ in probs:
-                torch.mm(src, w.t(), out=dst)
+        # one hand-written launch (x3 GEMMs above GEMM_MAX_ROWS rows; the library for fp64 and off the GPU)
+        kernels.gemm_group([(src, w, True, None, dst, False)
+                            for src, w, dst in zip(_blocks(c), (w0, w1, w2), _blocks(out))])
         ctx.save_for_backward(c, w0, w1, w2)
         return out
 
@@ -311,12 +308,8 @@ class _Mix3Bwd(Function):
     def forward(ctx, need_w, gout, c, w0, w1, w2):
         gc = torch.empty_like(c)
         ws = (w0, w1, w2)
-        probs = [(g, w, False, None, dst, False) for g, w, dst in zip(_blocks(gout), ws, _blocks(gc))]
-        if c.is_cuda:  # input gradients: one launch (x3 GEMMs above GEMM_MAX_ROWS rows)
-            kernels.gemm_group(probs)
-        else:
-            for g, w, _, _, dst, _ in probs:
-                torch.mm(g, w, out=dst)
+        # input gradients: one launch (x3 GEMMs above GEMM_MAX_ROWS rows)
+        kernels.gemm_group([(g, w, False, None, dst, False) for g, w, dst in zip(_blocks(gout), ws, _blocks(gc))])
         # weight gradients: one grouped TN launch (sums over the rows)
         gws = [torch.empty_like(w) if need else None for w, need in zip(ws, need_w)]
         tn = [{"A": g, "B": src, "C": gw} for g, src, gw in zip(_blocks(gout), _blocks(c), gws) if gw is not None]
