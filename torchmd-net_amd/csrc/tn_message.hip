@@ -60,6 +60,8 @@ template <typename T, typename CP = const T*, typename OP = T*> struct ArgsT {
   const int32_t* prow;      // [E] or NULL (per-edge rows)
   const int32_t* pedge;     // [np] the canonical edge of each pair slot
   int np;                   // pair slots
+  // the embedding destination pass in groups of four channel blocks (H > 256; last, the layout above unchanged)
+  int c0;                   // first channel of this launch (else 0)
 };
 template <typename T> using Args = ArgsT<T>;
 
@@ -208,10 +210,25 @@ __global__ __launch_bounds__(64 * S) void k_embed_fwd(AT A) {
 }
 
 // ---------------------------------------------------------------- embedding backward
+// store (add = false) or accumulate into p[i]; the dual form per part, a NULL part not touched
+template <typename T> __device__ __forceinline__ void put(T* p, size_t i, T v, bool add) {
+  p[i] = add ? p[i] + v : v;
+}
+template <typename T>
+__device__ __forceinline__ void put(node::DOut<T> p, size_t i, node::Dual<T> v, bool add) {
+  if (p.v) p.v[i] = add ? p.v[i] + v.v : v.v;
+  if (p.d) p.d[i] = add ? p.d[i] + v.d : v.d;
+}
+
 // destination pass: gP[n], gW[e'], gC[e'], gu[e'].  One wave per node covering all NB channel
 // blocks, so the per-edge channel sums (gC, gu) finish inside the wave: plain stores, deterministic.
-template <typename T, int NB, int S, typename AT = Args<T>>
+// GRP (more than 256 channels): one launch per group of four blocks from channel A.c0 on, in stream
+// order; the groups after the first (c0 > 0) add their sums to the first's -- the same lane of the same
+// wave in every group, still deterministic.  (A template switch: the one-launch form keeps its registers.)
+template <typename T, int NB, int S, typename AT = Args<T>, bool GRP = false>
 __global__ __launch_bounds__(64 * S) void k_embed_bwd_dst(AT A) {
+  const int c0 = GRP ? A.c0 : 0;
+  const bool add = GRP && A.c0 > 0;
   TMD_RED(T, S > 1 ? (S - 1) * NB * TMD_WAVE : 1)
   zero_tail_rows(A, A.gW, 3 * A.H);
   zero_tail_rows(A, A.gC, 1);
@@ -221,7 +238,7 @@ __global__ __launch_bounds__(64 * S) void k_embed_bwd_dst(AT A) {
   T g[NB][9], gPn[NB], Pn[NB];
 #pragma unroll
   for (int c = 0; c < NB; ++c) {
-    const int h = c * TMD_WAVE + lane;
+    const int h = c0 + c * TMD_WAVE + lane;
     const int hc = h < A.H ? h : 0;
     ldc(g[c], A.gE + (size_t)n * A.H + hc, A.nh);
     Pn[c] = A.P[(size_t)n * A.H + hc];
@@ -243,7 +260,7 @@ __global__ __launch_bounds__(64 * S) void k_embed_bwd_dst(AT A) {
       const auto wr = A.W + (size_t)kk[j] * A.ldw;
 #pragma unroll
       for (int c = 0; c < NB; ++c) {
-        const int h = c * TMD_WAVE + lane;
+        const int h = c0 + c * TMD_WAVE + lane;
         const int hc = h < A.H ? h : 0;
         qv[j][c] = A.Q[(size_t)m[j] * A.H + hc];
         wv[j][c][0] = wr[hc]; wv[j][c][1] = wr[A.H + hc]; wv[j][c][2] = wr[2 * A.H + hc];
@@ -261,7 +278,7 @@ __global__ __launch_bounds__(64 * S) void k_embed_bwd_dst(AT A) {
       T gc = T(0), gux = T(0), guy = T(0), guz = T(0);
 #pragma unroll
       for (int c = 0; c < NB; ++c) {
-        const int h = c * TMD_WAVE + lane;
+        const int h = c0 + c * TMD_WAVE + lane;
         const bool on = h < A.H;
         const T z = Pn[c] + qv[j][c];
         const T w1 = wv[j][c][0], w2 = wv[j][c][1], w3 = wv[j][c][2];
@@ -297,17 +314,17 @@ __global__ __launch_bounds__(64 * S) void k_embed_bwd_dst(AT A) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         if (j == 1 && !two) break;
-        A.gC[kk[j]] = red4[j][0];
-        A.gu[3 * kk[j]] = red4[j][1];
-        A.gu[3 * kk[j] + 1] = red4[j][2];
-        A.gu[3 * kk[j] + 2] = red4[j][3];
+        put(A.gC, kk[j], red4[j][0], add);
+        put(A.gu, 3 * kk[j], red4[j][1], add);
+        put(A.gu, 3 * kk[j] + 1, red4[j][2], add);
+        put(A.gu, 3 * kk[j] + 2, red4[j][3], add);
       }
     }
   }
   if (!fold_waves<T, NB, S>(gPn, red)) return;
 #pragma unroll
   for (int c = 0; c < NB; ++c) {
-    const int h = c * TMD_WAVE + lane;
+    const int h = c0 + c * TMD_WAVE + lane;
     if (h < A.H) A.gP[(size_t)n * A.H + h] = gPn[c];
   }
 }
@@ -704,15 +721,19 @@ static int launch_embed_bwd_dst(const Args<T>& A, hipStream_t st) {
     return v <= 0 ? 0 : v >= 8 ? 8 : v >= 4 ? 4 : v >= 2 ? 2 : 1;
   }();
   const int s = env_s ? env_s : (A.n < 8192 ? 8 : 2);
-#define TMD_EBD(NB)                                                                                   \
-  if (s == 1) hipLaunchKernelGGL((k_embed_bwd_dst<T, NB, 1>), g, dim3(64), 0, st, A);                 \
-  else if (s == 2) hipLaunchKernelGGL((k_embed_bwd_dst<T, NB, 2>), g, dim3(128), 0, st, A);           \
-  else if (s == 4) hipLaunchKernelGGL((k_embed_bwd_dst<T, NB, 4>), g, dim3(256), 0, st, A);           \
-  else hipLaunchKernelGGL((k_embed_bwd_dst<T, NB, 8>), g, dim3(512), 0, st, A);
-  if (A.nblk == 1) { TMD_EBD(1) }
-  else if (A.nblk == 2) { TMD_EBD(2) }
-  else if (A.nblk <= 4) { TMD_EBD(4) }
-  else return kUnsupported;
+#define TMD_EBD(NB, GRP)                                                                              \
+  using AT = Args<T>;                                                                                 \
+  if (s == 1) hipLaunchKernelGGL((k_embed_bwd_dst<T, NB, 1, AT, GRP>), g, dim3(64), 0, st, G);        \
+  else if (s == 2) hipLaunchKernelGGL((k_embed_bwd_dst<T, NB, 2, AT, GRP>), g, dim3(128), 0, st, G);  \
+  else if (s == 4) hipLaunchKernelGGL((k_embed_bwd_dst<T, NB, 4, AT, GRP>), g, dim3(256), 0, st, G);  \
+  else hipLaunchKernelGGL((k_embed_bwd_dst<T, NB, 8, AT, GRP>), g, dim3(512), 0, st, G);
+  Args<T> G = A;
+  if (A.nblk == 1) { TMD_EBD(1, false) }
+  else if (A.nblk == 2) { TMD_EBD(2, false) }
+  else if (A.nblk <= 4) { TMD_EBD(4, false) }
+  else {  // groups of four channel blocks (the last group's blocks past H are dead, as nblk == 3's fourth)
+    for (G.c0 = 0; G.c0 < A.H; G.c0 += 4 * TMD_WAVE) { TMD_EBD(4, true) }
+  }
 #undef TMD_EBD
   return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
 }
@@ -909,7 +930,11 @@ static int embed_bwd2(int n_nodes, int hidden, const int32_t* row_ptr, const int
     if (a.nblk == 1) hipLaunchKernelGGL((k_embed_bwd_dst<D, 1, 4, DA>), g, dim3(256), 0, st, a);
     else if (a.nblk == 2) hipLaunchKernelGGL((k_embed_bwd_dst<D, 2, 4, DA>), g, dim3(256), 0, st, a);
     else if (a.nblk <= 4) hipLaunchKernelGGL((k_embed_bwd_dst<D, 4, 4, DA>), g, dim3(256), 0, st, a);
-    else return kUnsupported;
+    else {  // groups of four channel blocks, as launch_embed_bwd_dst
+      for (a.c0 = 0; a.c0 < a.H; a.c0 += 4 * TMD_WAVE)
+        hipLaunchKernelGGL((k_embed_bwd_dst<D, 4, 4, DA, true>), g, dim3(256), 0, st, a);
+      a.c0 = 0;
+    }
   }
   if (dQ) hipLaunchKernelGGL((k_embed_bwd_src<D, 4, DA>), gs, dim3(256), 0, st, a);
   return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
