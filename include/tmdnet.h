@@ -42,6 +42,16 @@ enum { TMDNET_BWD2_ACC_EDGE = 8, TMDNET_BWD2_ACC_GVEC = 16 };
  * source) instead of the merged pass that serves both roles of a node from one read of each pair row
  * (the default from 16384 nodes; same results up to summation order). */
 enum { TMDNET_ET_TWO_PASS = 64 };
+/* tmdnet_et_message_fwd flags / tmdnet_et_message_bwd accumulate bit: pk / pv hold the ACTIVATED rows
+ * S = act(pre) and (backward) dpk / dpv hold D = act'(pre) * d pre / d r, as tmdnet_proj_act_f32 writes
+ * them; the edge kernels then evaluate no dk / dv activation (the attention activation is unchanged).
+ * The backward takes it in dr mode only, without gpk / gpv (the raw-row gradient cannot be formed from
+ * S): gdist == NULL or gpk / gpv != NULL -> TMDNET_BAD_ARGUMENT, nothing written.  It runs the one-grid or
+ * the two-launch form, never the merged pass.
+ * Values in use -- forward flags: 4 (V_PLANAR), 128 (PREACT), 0xff00 (ACT); backward accumulate: 1, 2
+ * (ACC_VEC_RESIDUAL, ACC_EDGE), 4, 32 (ACC_GRADS), 64 (TWO_PASS), 128, 0xff00; _bwd2 flags: 4, 8, 16
+ * (BWD2_ACC_*), 0xff00. */
+enum { TMDNET_ET_PREACT = 128 };
 /* Activations of the ET message entry points (tmdnet_et_message_fwd flags, _bwd accumulate, _bwd2 /
  * _bwd2_ex flags): bits 8-11 = the dk / dv projections' activation (reference EquivariantMultiHeadAttention
  * `activation`, torchmd_et.py:285-291), bits 12-15 = the attention activation (`attn_activation`,
@@ -750,6 +760,17 @@ int tmdnet_gemm_x3w_f32(int M, int N, int K, const void* A, int lda, const void*
 int tmdnet_proj_split_f32(int N, int K, const void* W, int ldw, void* Wp, void* stream);
 int tmdnet_proj_f32(int M, int N, int K, const void* A, int lda, const void* Wp, long long piece_stride,
                     const void* bias, void* C, int ldc, void* stream);
+/* tmdnet_proj_f32 with the dk / dv activation in the GEMM's epilogue -- the rows the ET message kernels read
+ * under TMDNET_ET_PREACT.  With pre = A W^T + bias (the bits tmdnet_proj_f32 writes: same split, same
+ * accumulation order):
+ *   S [M][N] = act(pre)                          (act: TMDNET_ACT_*, evaluated as the edge kernels do)
+ *   D [M][N] = act'(pre) * (dA W^T)              (dA, D nullable together: dA = d A / d r at the same rows,
+ *                                                 row stride lda; no bias on the derivative)
+ * S and D share the row stride ldc.  Envelope and alignment as tmdnet_proj_f32 (else TMDNET_UNSUPPORTED,
+ * nothing launched; dA and D 16-byte aligned too); D without dA, or an unknown act: TMDNET_BAD_ARGUMENT. */
+int tmdnet_proj_act_f32(int M, int N, int K, const void* A, const void* dA, int lda, const void* Wp,
+                        long long piece_stride, const void* bias, int act, void* S, void* D, int ldc,
+                        void* stream);
 
 /* The ET message with the dk/dv projection FUSED in (reference torchmd_et.py:282-291 + :314-347, the
  * RBF of models/utils.py:272-344): tmdnet_et_message_fwd's outputs without the projection rows.  Per

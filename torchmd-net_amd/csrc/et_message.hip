@@ -149,6 +149,13 @@ __device__ __forceinline__ void act(const T (&x)[V], bool has, T (&s)[V], T (&ds
     }
   }
 }
+// TMDNET_ET_PREACT: the row segment already holds the activated values S = act(pre) (written by the
+// projection GEMM's epilogue, tmdnet_proj_act_f32); an absent projection is still the constant 1.
+template <typename T, int V>
+__device__ __forceinline__ void preact(const T (&x)[V], bool has, T (&s)[V]) {
+#pragma unroll
+  for (int i = 0; i < V; ++i) s[i] = has ? x[i] : T(1);
+}
 // Branch-free optional load: an absent projection reads a valid dummy row (result ignored).
 template <typename T> __device__ __forceinline__ const T* opt(const T* p, size_t off, const T* dummy) {
   return p ? p + off : dummy;
@@ -304,7 +311,8 @@ __device__ __forceinline__ void edge_chunks(const Args<T>& A, int b, int e, int 
 // ------------------------------------------------------------------ forward
 // ORD: nodes visited in the caller's `order` (cell order for large periodic systems, so the waves in
 // flight gather from a compact spatial window of source rows).
-template <typename T, int V, int S, int CS, bool ORD, bool GA = true>
+// PRE: pk / pv hold the activated rows (TMDNET_ET_PREACT): no dk / dv activation here.
+template <typename T, int V, int S, int CS, bool ORD, bool GA = true, bool PRE = false>
 __global__ __launch_bounds__(256) void k_fwd(Args<T> A) {
   const int AKV = GA ? A.act_kv : kActSilu, AAT = GA ? A.act_at : kActSilu;  // GA: runtime codes
   __shared__ T lds[S > 1 ? 4 * 64 * 4 * V : 1];
@@ -348,11 +356,20 @@ __global__ __launch_bounds__(256) void k_fwd(Args<T> A) {
       ldv<T, V>(w2, vecs + 2 * vcd);
       pre();
       if (!hw) { zero(w0); zero(w1); zero(w2); }
-      T dk[V], dvx[V], dv1[V], dv2[V], dd[V];
-      act<T, V>(st.k, hk, dk, dd, AKV);
-      act<T, V>(st.x, hv, dvx, dd, AKV);
-      act<T, V>(st.a, hv, dv1, dd, AKV);
-      act<T, V>(st.b, hv, dv2, dd, AKV);
+      T dk[V], dvx[V], dv1[V], dv2[V];
+      if constexpr (PRE) {
+        (void)AKV;
+        preact<T, V>(st.k, hk, dk);
+        preact<T, V>(st.x, hv, dvx);
+        preact<T, V>(st.a, hv, dv1);
+        preact<T, V>(st.b, hv, dv2);
+      } else {
+        T dd[V];
+        act<T, V>(st.k, hk, dk, dd, AKV);
+        act<T, V>(st.x, hv, dvx, dd, AKV);
+        act<T, V>(st.a, hv, dv1, dd, AKV);
+        act<T, V>(st.b, hv, dv2, dd, AKV);
+      }
       T part = T(0);
 #pragma unroll
       for (int i = 0; i < V; ++i) part += q[i] * kk[i] * dk[i];
@@ -415,8 +432,12 @@ __device__ __forceinline__ void zero_pad_rows(const Args<T>& A, int blk, int nwg
 
 // AG: TMDNET_ACC_GRADS in the training form -- the injected per-edge projection cotangents are loaded
 // with the edge's other loads (not read back after the math: one memory round trip per edge fewer)
-template <typename T, int V, int S, int CS, bool DR, bool AG = false, bool GA = true>
+// PRE (TMDNET_ET_PREACT; DR without gpk / gpv only): pk / pv hold S = act(pre), dpk / dpv hold
+// D = act'(pre) * d pre / d r -- the activation derivative only ever multiplies d pre / d r here, so
+// g_r = <gs q k, D_k> + <gx a vx, D_x> + <gv1e v1, D_1> + <gv2e v2, D_2> with no activation evaluated.
+template <typename T, int V, int S, int CS, bool DR, bool AG = false, bool GA = true, bool PRE = false>
 __device__ __forceinline__ void bwd_dst_body(const Args<T>& A, int blk, int nwg) {
+  static_assert(!PRE || (DR && !AG), "pre-activated rows: the dr-mode force pass only");
   const int AKV = GA ? A.act_kv : kActSilu, AAT = GA ? A.act_at : kActSilu;  // GA: runtime codes
   __shared__ T lds[S > 1 ? 4 * 64 * V : 1];
   const Geo G = geo<S, CS, false>(A.n, A.L, nullptr, A.xcd, blk, nwg);
@@ -497,11 +518,20 @@ __device__ __forceinline__ void bwd_dst_body(const Args<T>& A, int blk, int nwg)
       const T (&px)[V] = st.x;
       const T (&p1)[V] = st.a;
       const T (&p2)[V] = st.b;
-      T dk[V], ddk[V], dvx[V], dv1[V], dv2[V], ddx[V], dd1[V], dd2[V];
-      act<T, V>(pk, hk, dk, ddk, AKV);
-      act<T, V>(px, hv, dvx, ddx, AKV);
-      act<T, V>(p1, hv, dv1, dd1, AKV);
-      act<T, V>(p2, hv, dv2, dd2, AKV);
+      constexpr int VD = PRE ? 1 : V;  // (PRE: no activation derivatives)
+      T dk[V], ddk[VD], dvx[V], dv1[V], dv2[V], ddx[VD], dd1[VD], dd2[VD];
+      if constexpr (PRE) {
+        (void)AKV;
+        preact<T, V>(pk, hk, dk);
+        preact<T, V>(px, hv, dvx);
+        preact<T, V>(p1, hv, dv1);
+        preact<T, V>(p2, hv, dv2);
+      } else {
+        act<T, V>(pk, hk, dk, ddk, AKV);
+        act<T, V>(px, hv, dvx, ddx, AKV);
+        act<T, V>(p1, hv, dv1, dd1, AKV);
+        act<T, V>(p2, hv, dv2, dd2, AKV);
+      }
       T part = T(0), ga = T(0), gu0 = T(0), gu1 = T(0), gu2 = T(0);
 #pragma unroll
       for (int i = 0; i < V; ++i) {
@@ -517,16 +547,26 @@ __device__ __forceinline__ void bwd_dst_body(const Args<T>& A, int blk, int nwg)
       const ActF<T> sa(part, AAT);
       const T a = sa.s * Ce;
       const T gs = ga * Ce * sa.d(part);
+      // the projection gradient (PRE: its factor in front of act'(pre), which D carries)
       T gpk[V], gpx[V], gp1[V], gp2[V];
 #pragma unroll
       for (int i = 0; i < V; ++i) {
         gq[i] += gs * kk[i] * dk[i];
-        gpk[i] = gs * q[i] * kk[i] * ddk[i];
-        gpx[i] = gx[i] * a * vx[i] * ddx[i];
-        const T gv1e = g0[i] * w0[i] + g1[i] * w1[i] + g2[i] * w2[i];
-        gp1[i] = gv1e * v1[i] * dd1[i];
-        const T gv2e = g0[i] * u0 + g1[i] * u1 + g2[i] * u2;
-        gp2[i] = gv2e * v2[i] * dd2[i];
+        if constexpr (PRE) {
+          gpk[i] = gs * q[i] * kk[i];
+          gpx[i] = gx[i] * a * vx[i];
+          const T gv1e = g0[i] * w0[i] + g1[i] * w1[i] + g2[i] * w2[i];
+          gp1[i] = gv1e * v1[i];
+          const T gv2e = g0[i] * u0 + g1[i] * u1 + g2[i] * u2;
+          gp2[i] = gv2e * v2[i];
+        } else {
+          gpk[i] = gs * q[i] * kk[i] * ddk[i];
+          gpx[i] = gx[i] * a * vx[i] * ddx[i];
+          const T gv1e = g0[i] * w0[i] + g1[i] * w1[i] + g2[i] * w2[i];
+          gp1[i] = gv1e * v1[i] * dd1[i];
+          const T gv2e = g0[i] * u0 + g1[i] * u1 + g2[i] * u2;
+          gp2[i] = gv2e * v2[i] * dd2[i];
+        }
       }
       const T gc = group_sum(head_leader ? ga * sa.s : T(0), A.L);
       gu0 = group_sum(gu0, A.L);
@@ -539,7 +579,7 @@ __device__ __forceinline__ void bwd_dst_body(const Args<T>& A, int blk, int nwg)
           grr += (hk ? gpk[i] * dpk_[i] : T(0)) +
                  (hv ? gpx[i] * dpx_[i] + gp1[i] * dp1_[i] + gp2[i] * dp2_[i] : T(0));
         grr = group_sum(grr, A.L);
-        if (on && (A.gpk || A.gpv)) {  // the recorded force pass also keeps the projection gradient
+        if (!PRE && on && (A.gpk || A.gpv)) {  // the recorded force pass also keeps the projection gradient
           if (hk && A.gpk) stv<T, V>(A.gpk + (size_t)k * A.ldpk + c0, gpk);
           if (hv && A.gpv) {
             T* gp = A.gpv + (size_t)k * A.ldpv + vo;
@@ -584,7 +624,7 @@ __device__ __forceinline__ void bwd_dst_body(const Args<T>& A, int blk, int nwg)
 // ------------------------------------------------------------------ backward, source pass
 // A wave group owns node j as SOURCE.  Row j lists edges m->j; each is read as its reverse j->m
 // (same dk/dv/cutoff, unit vector negated), m being the destination whose q/gx/gvec are gathered.
-template <typename T, int V, int S, int CS, bool GA = true>
+template <typename T, int V, int S, int CS, bool GA = true, bool PRE = false>
 __device__ __forceinline__ void bwd_src_body(const Args<T>& A, int blk, int nwg) {
   const int AKV = GA ? A.act_kv : kActSilu, AAT = GA ? A.act_at : kActSilu;  // GA: runtime codes
   __shared__ T lds[S > 1 ? 4 * 64 * 7 * V : 1];
@@ -640,11 +680,20 @@ __device__ __forceinline__ void bwd_src_body(const Args<T>& A, int blk, int nwg)
       const T (&px)[V] = st.x;
       const T (&p1)[V] = st.a;
       const T (&p2)[V] = st.b;
-      T dk[V], ddk[V], dvx[V], dv1[V], dv2[V], dd[V];
-      act<T, V>(pk, hk, dk, ddk, AKV);
-      act<T, V>(px, hv, dvx, dd, AKV);
-      act<T, V>(p1, hv, dv1, dd, AKV);
-      act<T, V>(p2, hv, dv2, dd, AKV);
+      T dk[V], dvx[V], dv1[V], dv2[V];
+      if constexpr (PRE) {
+        (void)AKV;
+        preact<T, V>(pk, hk, dk);
+        preact<T, V>(px, hv, dvx);
+        preact<T, V>(p1, hv, dv1);
+        preact<T, V>(p2, hv, dv2);
+      } else {
+        T ddk[V], dd[V];
+        act<T, V>(pk, hk, dk, ddk, AKV);
+        act<T, V>(px, hv, dvx, dd, AKV);
+        act<T, V>(p1, hv, dv1, dd, AKV);
+        act<T, V>(p2, hv, dv2, dd, AKV);
+      }
       T part = T(0), ga = T(0);
 #pragma unroll
       for (int i = 0; i < V; ++i) {
@@ -715,22 +764,22 @@ __device__ __forceinline__ void bwd_src_body(const Args<T>& A, int blk, int nwg)
 template <typename T, int V, bool DR>
 constexpr int bwd_min_waves() { return (DR && sizeof(T) == 4 && V <= 4) ? 3 : 1; }
 
-template <typename T, int V, int S, int CS, bool DR, bool AG = false, bool GA = true>
+template <typename T, int V, int S, int CS, bool DR, bool AG = false, bool GA = true, bool PRE = false>
 __global__ __launch_bounds__(256, (bwd_min_waves<T, V, DR>())) void k_bwd_dst(Args<T> A) {
-  bwd_dst_body<T, V, S, CS, DR, AG, GA>(A, blockIdx.x, gridDim.x);
+  bwd_dst_body<T, V, S, CS, DR, AG, GA, PRE>(A, blockIdx.x, gridDim.x);
 }
-template <typename T, int V, int S, int CS, bool GA = true>
+template <typename T, int V, int S, int CS, bool GA = true, bool PRE = false>
 __global__ __launch_bounds__(256) void k_bwd_src(Args<T> A) {
-  bwd_src_body<T, V, S, CS, GA>(A, blockIdx.x, gridDim.x);
+  bwd_src_body<T, V, S, CS, GA, PRE>(A, blockIdx.x, gridDim.x);
 }
 // Both passes in ONE grid (they only read the same inputs): blocks [0, split) run the destination
 // pass, [split, 2 split) the source pass.  Used for small systems, where one pass alone leaves most
 // of the chip idle and the launch gap between the two passes is a visible share of the layer.
-template <typename T, int V, int S, int CS, bool DR, bool AG = false, bool GA = true>
+template <typename T, int V, int S, int CS, bool DR, bool AG = false, bool GA = true, bool PRE = false>
 __global__ __launch_bounds__(256, (bwd_min_waves<T, V, DR>())) void k_bwd_both(Args<T> A) {
   const int split = (int)gridDim.x / 2;
-  if ((int)blockIdx.x < split) bwd_dst_body<T, V, S, CS, DR, AG, GA>(A, blockIdx.x, split);
-  else bwd_src_body<T, V, S, CS, GA>(A, blockIdx.x - split, split);
+  if ((int)blockIdx.x < split) bwd_dst_body<T, V, S, CS, DR, AG, GA, PRE>(A, blockIdx.x, split);
+  else bwd_src_body<T, V, S, CS, GA, PRE>(A, blockIdx.x - split, split);
 }
 
 // ------------------------------------------------------------------ backward, merged pass (dr mode)
@@ -1587,7 +1636,7 @@ static int et_launch_vs(Args<T> A, hipStream_t st) {
   // channel groups (CS = 2 / 4) are supported by the kernels but measured neutral (+-1 %) on the
   // C5 water box (tools/kbench.py), so one group is used.
   int cs = 1;
-  if (KIND == 1 || A.H % (cs * V) || (A.H / cs / V) & (A.H / cs / V - 1) || A.H / cs / V < A.lph ||
+  if (KIND == 1 || KIND == 11 || A.H % (cs * V) || (A.H / cs / V) & (A.H / cs / V - 1) || A.H / cs / V < A.lph ||
       A.H / cs / V > 64)
     cs = 1;
   A.HC = A.H / cs;
@@ -1612,6 +1661,11 @@ static int et_launch_k(const Args<T>& A, dim3 g, dim3 b, int nbn, hipStream_t st
   else if (KIND == 4) hipLaunchKernelGGL((k_bwd_dst<T, V, S, 1, true, false, GA>), g, b, 0, st, A);
   else if (KIND == 5) hipLaunchKernelGGL((k_bwd_both<T, V, S, 1, true, false, GA>), dim3(2 * nbn), b, 0, st, A);
   else if (KIND == 6) hipLaunchKernelGGL((k_bwd_both<T, V, S, 1, false, true, GA>), dim3(2 * nbn), b, 0, st, A);
+  // pre-activated rows (TMDNET_ET_PREACT): forward, dr-mode destination pass, source pass, both in one grid
+  else if (KIND == 10) hipLaunchKernelGGL((k_fwd<T, V, S, 1, ORD, GA, true>), g, b, 0, st, A);
+  else if (KIND == 11) hipLaunchKernelGGL((k_bwd_dst<T, V, S, 1, true, false, GA, true>), g, b, 0, st, A);
+  else if (KIND == 12) hipLaunchKernelGGL((k_bwd_src<T, V, S, 1, GA, true>), g, b, 0, st, A);
+  else if (KIND == 13) hipLaunchKernelGGL((k_bwd_both<T, V, S, 1, true, false, GA, true>), dim3(2 * nbn), b, 0, st, A);
   else if (KIND == 8 || KIND == 9) {
     // dynamic LDS: the node vectors of the block's 4 / S nodes, or the cross-wave reduction
     const size_t node = (size_t)(4 / S) * 12 * A.H, red = S > 1 ? 4 * 64 * 8 * V : 1;
@@ -1645,9 +1699,10 @@ static int et_launch_v(const Args<T>& A, hipStream_t st) {
   // wave (r04, tools/pair_probe.py; fewer nodes in flight per XCD, so more of each pair row's second read
   // hits L2); the backward passes are faster at 1 there (3.25 vs 3.52 ms)
   static const bool env_s_set = getenv("TMDNET_ET_S") != nullptr;
-  if (KIND == 0 && !env_s_set && (int)sizeof(T) * V <= 32) S = 4;
+  constexpr bool FWD = KIND == 0 || KIND == 10;
+  if (FWD && !env_s_set && (int)sizeof(T) * V <= 32) S = 4;
   static const int bwd_s = getenv("TMDNET_ET_BWD_S") ? atoi(getenv("TMDNET_ET_BWD_S")) : 0;  // tuning
-  if (KIND != 0 && bwd_s && (int)sizeof(T) * V <= 32) S = bwd_s >= 4 ? 4 : bwd_s >= 2 ? 2 : 1;
+  if (!FWD && bwd_s && (int)sizeof(T) * V <= 32) S = bwd_s >= 4 ? 4 : bwd_s >= 2 ? 2 : 1;
   if (S == 4) return et_launch_vs<T, V, (sizeof(T) * V <= 32 ? 4 : 1), KIND, ORD>(A, st);
   if (S == 2) return et_launch_vs<T, V, (sizeof(T) * V <= 32 ? 2 : 1), KIND, ORD>(A, st);
   return et_launch_vs<T, V, 1, KIND, ORD>(A, st);
@@ -1725,6 +1780,7 @@ static int fwd(int n, int H, int heads, const int32_t* row_ptr, const int32_t* s
   if (flags & TMDNET_ET_V_PLANAR) { A.planar = 1; A.vst = H; }
   A.xo = (T*)xo;
   A.veco = (T*)veco;
+  if (flags & TMDNET_ET_PREACT) return order ? et_launch<T, 10, true>(V, A, st) : et_launch<T, 10, false>(V, A, st);
   return order ? et_launch<T, 0, true>(V, A, st) : et_launch<T, 0, false>(V, A, st);
 }
 
@@ -1757,6 +1813,14 @@ static int bwd(int n, int H, int heads, const int32_t* row_ptr, const int32_t* s
   if (dr && ((A.pk && !dpk) || (A.pv && !dpv))) return kBadArgument;
   if (!dr && ((A.pk && !gpk) || (A.pv && !gpv))) return kBadArgument;
   const int fuse_nodes = tune_get(TMDNET_TUNE_ET_BOTH_MAX_NODES);
+  if (acc & TMDNET_ET_PREACT) {
+    // pk / pv = S, dpk / dpv = D: the dr-mode force pass only (the raw-row gradient cannot be formed from
+    // S); the one-grid or the two-launch form (the merged pass has no pre-activated variant)
+    if (!dr || gpk || gpv) return kBadArgument;
+    if (n < fuse_nodes) return et_launch<T, 13, false>(V, A, st);
+    if ((rc = et_launch<T, 11, false>(V, A, st))) return rc;
+    return et_launch<T, 12, false>(V, A, st);
+  }
   const bool ag = !dr && (acc & TMDNET_ACC_GRADS) && (A.pk || A.pv);  // injected projection cotangents
   // dr mode: both roles in one pass over the rows (k_bwd_merged)
   // (tuning: TMDNET_ET_MERGED=0 off, 1 stream-prefetching variant, 2 loads per edge in the body).

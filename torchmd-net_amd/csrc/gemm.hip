@@ -851,6 +851,125 @@ __global__ __launch_bounds__(256) void k_proj_x3(Args P) {
   }
 }
 
+// k_proj_x3 with the dk / dv activation in the epilogue (tmdnet_proj_act_f32): S = act(A W^T + bias) and,
+// DER, D = act'(A W^T + bias) * (dA W^T) from a second accumulator set over the same W fragments -- the
+// rows the ET edge kernels read pre-activated (TMDNET_ET_PREACT) instead of evaluating the activation per
+// edge and pass.  Same tiles, staging, split and accumulation order as k_proj_x3 (pre = acc + bias is the
+// same bits), the activation by the edge kernels' own functions (Silu / ActF of common.h), one 16-byte
+// store per lane, row block and output.
+struct ActArgs {
+  Args p;           // A, Wp, bias as k_proj_x3; C = S
+  const float* dA;  // d A / d r rows (lda as A), DER
+  float* D;         // [M][N], ldc as S, DER
+  int act;          // ActCode
+};
+
+template <int KS, int MB, int BN, bool DER>
+__global__ __launch_bounds__(256) void k_proj_act_x3(ActArgs Q) {
+  const Args& P = Q.p;
+  constexpr int K = 32 * KS, LD = K + 8;
+  __shared__ __attribute__((aligned(16))) unsigned short w[3][BN][LD];
+  __shared__ __attribute__((aligned(16))) float sb[BN];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n0 = blockIdx.x * BN;
+  const int m0 = (blockIdx.y * 4 + wave) * (16 * MB);
+  const int nr = min(BN, P.N - n0);
+  const int kq = 8 * (lane >> 4);
+  constexpr int ND = DER ? 2 : 1;  // operand sets: A (and dA)
+  float4 ar[ND][MB][KS][2];
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb) {
+    const size_t ro = (size_t)min(m0 + 16 * mb + (lane & 15), P.M - 1) * P.lda + kq;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      ar[0][mb][ks][0] = *reinterpret_cast<const float4*>(P.A + ro + 32 * ks);
+      ar[0][mb][ks][1] = *reinterpret_cast<const float4*>(P.A + ro + 32 * ks + 4);
+      if constexpr (DER) {
+        ar[1][mb][ks][0] = *reinterpret_cast<const float4*>(Q.dA + ro + 32 * ks);
+        ar[1][mb][ks][1] = *reinterpret_cast<const float4*>(Q.dA + ro + 32 * ks + 4);
+      }
+    }
+  }
+  constexpr int CH = K / 8;
+  constexpr int NL = (3 * BN * CH + 255) / 256;
+  u4 stg[NL];
+#pragma unroll
+  for (int i = 0; i < NL; ++i) {
+    const int c = threadIdx.x + 256 * i;
+    const int p = c / (BN * CH), rc = c % (BN * CH), n = rc / CH, k = (rc % CH) * 8;
+    if (c < 3 * BN * CH)
+      stg[i] = *reinterpret_cast<const u4*>(P.Wp + p * P.pstride + (size_t)min(n0 + n, P.N - 1) * K + k);
+  }
+#pragma unroll
+  for (int i = 0; i < NL; ++i) {
+    const int c = threadIdx.x + 256 * i;
+    const int p = c / (BN * CH), rc = c % (BN * CH), n = rc / CH, k = (rc % CH) * 8;
+    if (c < 3 * BN * CH) *reinterpret_cast<u4*>(&w[p][n][k]) = stg[i];
+  }
+  if (threadIdx.x < BN) sb[threadIdx.x] = P.bias ? P.bias[min(n0 + (int)threadIdx.x, P.N - 1)] : 0.f;
+  bf8 a[ND][MB][KS][3];
+#pragma unroll
+  for (int d = 0; d < ND; ++d)
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) split8(ar[d][mb][ks][0], ar[d][mb][ks][1], a[d][mb][ks]);
+  __syncthreads();
+  if (m0 >= P.M) return;
+  const int code = Q.act;
+  for (int nb = 0; nb < nr; nb += 16) {
+    bf8 b[KS][3];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        b[ks][p] = *reinterpret_cast<const bf8*>(&w[p][nb + (lane & 15)][32 * ks + kq]);
+    f4 acc[ND][MB];
+#pragma unroll
+    for (int d = 0; d < ND; ++d)
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb) acc[d][mb] = f4{0.f, 0.f, 0.f, 0.f};
+    constexpr int TW[6] = {2, 1, 0, 1, 0, 0}, TA[6] = {0, 1, 2, 0, 1, 0};  // small terms first, as k_proj_x3
+#pragma unroll
+    for (int t = 0; t < 6; ++t)
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+        for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+          for (int d = 0; d < ND; ++d)
+            acc[d][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[ks][TW[t]], a[d][mb][ks][TA[t]], acc[d][mb], 0, 0, 0);
+    const int nl = nb + 4 * (lane >> 4);
+    const f4 bv = *reinterpret_cast<const f4*>(&sb[nl]);
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) {
+      const int m = m0 + 16 * mb + (lane & 15);
+      const f4 pre = acc[0][mb] + bv;
+      f4 s, ds;
+      if (code == kActSilu) {  // (one wave-uniform branch per row block, the math as the edge kernels')
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const Silu<float> f(pre[i]);
+          s[i] = f.s;
+          ds[i] = DER ? f.d(pre[i]) : 0.f;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const ActF<float> f(pre[i], code);
+          s[i] = f.s;
+          ds[i] = DER ? f.d(pre[i]) : 0.f;
+        }
+      }
+      if (m < P.M) {
+        const size_t o = (size_t)m * P.ldc + n0 + nl;
+        *reinterpret_cast<f4*>(P.C + o) = s;
+        if constexpr (DER) *reinterpret_cast<f4*>(Q.D + o) = ds * acc[1][mb];
+      }
+    }
+  }
+}
+
 // B [K][N] (row-major, ldb) -> the three exact bf16 pieces of B^T, Bp [3][N][K]: the split of a weight that
 // multiplies from the right untransposed (an input gradient g_y W of a Linear y = x W^T), so that
 // k_gemm_x3 reads it as the k-contiguous [N][K] operand.  One thread per 4 consecutive k of one n.
@@ -1901,6 +2020,41 @@ extern "C" int tmdnet_proj_f32(int M, int N, int K, const void* A, int lda, cons
     if (mb == 4) TMD_PROJ(1, 4, 64); else TMD_PROJ(1, 2, 64);
   }
 #undef TMD_PROJ
+  return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
+}
+
+// S [M][N] = act(A W^T + bias) and (dA, D given) D = act'(A W^T + bias) * (dA W^T): tmdnet_proj_f32's
+// envelope and tiles with the ET dk / dv activation in the epilogue (k_proj_act_x3).
+extern "C" int tmdnet_proj_act_f32(int M, int N, int K, const void* A, const void* dA, int lda, const void* Wp,
+                                   long long piece_stride, const void* bias, int act, void* S, void* D, int ldc,
+                                   void* stream) {
+  if (M < 0 || N <= 0 || K <= 0 || !A || !Wp || !S || act < kActSilu || act > kActSigmoid) return kBadArgument;
+  if (D && !dA) return kBadArgument;
+  if (M == 0) return kOk;
+  if ((K != 32 && K != 64) || N % 16 || lda < K || ldc < N || lda % 4 || ldc % 4 || piece_stride < (long long)N * K)
+    return kUnsupported;
+  if ((((uintptr_t)A) | ((uintptr_t)dA) | ((uintptr_t)Wp) | ((uintptr_t)S) | ((uintptr_t)D) | ((uintptr_t)bias)) & 15)
+    return kUnsupported;
+  const bool der = D != nullptr;
+  // tiles: tmdnet_proj_f32's (128 x 64; 256 x 128 from 65536 rows at K = 64, without the derivative: its
+  // second operand and accumulator set double the row registers)
+  const bool big = M >= 65536 && K == 64 && !der;
+  const int bn = big ? 128 : 64, mb = big ? 4 : 2;
+  proj::ActArgs Q{{M, N, lda, ldc, piece_stride, (const float*)A, (const unsigned short*)Wp, (const float*)bias,
+                   (float*)S},
+                  (const float*)dA, (float*)D, act};
+  const dim3 g((N + bn - 1) / bn, (M + 64 * mb - 1) / (64 * mb));
+  hipStream_t st = (hipStream_t)stream;
+#define TMD_PROJ_ACT(KS_, MB_, BN_, DER_) \
+  hipLaunchKernelGGL((proj::k_proj_act_x3<KS_, MB_, BN_, DER_>), g, dim3(256), 0, st, Q)
+  if (K == 64) {
+    if (big) TMD_PROJ_ACT(2, 4, 128, false);
+    else if (der) TMD_PROJ_ACT(2, 2, 64, true);
+    else TMD_PROJ_ACT(2, 2, 64, false);
+  } else {
+    if (der) TMD_PROJ_ACT(1, 2, 64, true); else TMD_PROJ_ACT(1, 2, 64, false);
+  }
+#undef TMD_PROJ_ACT
   return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
 }
 

@@ -22,6 +22,7 @@ ACC_GRADS = 32
 ET_V_PLANAR = 4
 BWD2_ACC_EDGE, BWD2_ACC_GVEC = 8, 16
 ET_TWO_PASS = 64
+ET_PREACT = 128  # pk / pv (dpk / dpv) hold the activated rows S (D) of tmdnet_proj_act_f32
 
 _STATUS = {1: "bad argument", 2: "unsupported configuration", 3: "kernel launch failed",
            4: "workspace too small"}
@@ -131,6 +132,7 @@ SIGNATURES = {
     "tmdnet_fep_frags_bytes": (SZ, [ctypes.c_longlong, I]),
     "tmdnet_fep_frags_f32": (I, [ctypes.c_longlong, I, P, P, P, D, D, I, P, P, P]),
     "tmdnet_proj_f32": (I, [I, I, I, P, I, P, ctypes.c_longlong, P, P, I, P]),
+    "tmdnet_proj_act_f32": (I, [I, I, I, P, P, I, P, ctypes.c_longlong, P, I, P, P, I, P]),
     "tmdnet_mse2_fwd": (I, [I, I, P, P, D, I, P, P, D, P, P]),
     "tmdnet_mse2_bwd": (I, [I, I, P, P, D, I, P, P, D, P, P, P, P]),
     "tmdnet_build_info": (ctypes.c_char_p, []),

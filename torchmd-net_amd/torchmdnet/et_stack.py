@@ -144,6 +144,12 @@ FUSED_BWD = FEP_BWD == "fused"
 # MI355X: C2 1.076 -> 1.063 ms, C4 0.932 -> 0.917 ms, C5 73.9 -> 71.3 ms; the eager training step
 # is within its run-to-run noise (29-35 ms).  TMDNET_DR=0 turns it off.
 DR_MODE = os.environ.get("TMDNET_DR", "auto")
+# Pre-activated dk/dv rows for the force evaluation (energy, or energy + forces, with no second order
+# expected): the projection GEMM's epilogue writes S = act(pre) and, when a backward can follow,
+# D = act'(pre) * d pre / d r (kernels.proj_act, one launch instead of the projection and its r-derivative),
+# and the three edge kernels read them (nat.ET_PREACT) instead of each evaluating the activation on 4H
+# values per edge.  A backward that needs the raw rows re-forms them (_act_pkv).  TMDNET_ET_PREACT=0: off.
+PREACT = os.environ.get("TMDNET_ET_PREACT", "1") not in ("0", "off")
 # second order of the force pass (force-matching training): "hand" = the hand-scheduled adjoint
 # (_second_order), "composite" = autograd over the recomputed stack (the reference for tests / A-B)
 SECOND_ORDER = os.environ.get("TMDNET_ET_SECOND_ORDER", "hand")
@@ -249,6 +255,8 @@ class _Meta:
         self.fep = False        # the forward runs the fused-projection edge kernel (FEP)
         self.fep_imgs = None    # per layer: its weight image (kernels.fep_split), made by the forward
         self.grad_mode = True   # torch.is_grad_enabled() where the stack was called (a backward can follow)
+        self.pre = None         # (S_all, D_all or None): the pre-activated rows of this forward (PREACT)
+        self.r_grad = True      # the distances take a gradient (a force pass can follow the forward)
 
     def split(self, params):
         return [params[i * self.np:(i + 1) * self.np] for i in range(self.n_layers)]
@@ -413,7 +421,7 @@ def _act_pkv(meta, acts, l, f):
     """Layer l's forward activations, with its projection rows formed now if the fused forward (FEP)
     skipped them (a backward that contracts them: training form, or the unfused dr-mode pass)."""
     a = acts[l]
-    if a[7] is None and meta.fep_imgs is not None and meta.D:
+    if a[7] is None and (meta.fep_imgs is not None or meta.pre is not None) and meta.D:
         if meta.batched:  # every layer's rows in one GEMM, as the unfused forward lays them out: the
             # message backward reads d(dk,dv)/dr with the projection rows' leading dimension
             pkv_all, D = meta.dkv_proj(_pair_f(meta, f)), meta.D
@@ -438,7 +446,21 @@ def _forward_layers(meta, x, f, C, u, params, r=None, want_bwd=False):
     if not fep:
         meta.fep_imgs = None  # (the backward's fused path keys on them: none from an earlier forward)
     fp = _pair_f(meta, f) if (D and not fep) else f
-    pkv_all = meta.dkv_proj(fp) if (meta.batched and D and not fep) else None
+    # pre-activated rows (PREACT): the force-evaluation form on the unfused row path -- S (and, with a
+    # backward to follow, D from f' at the pair rows) from one GEMM launch; nothing outside its envelope
+    meta.pre = None
+    if (PREACT and D and not fep and meta.batched and meta.rbf is not None and r is not None
+            and meta.pairs is not None and x.is_cuda and x.dtype == torch.float32 and fp.shape[0] > 0
+            and (not want_bwd or (meta.r_grad and not _EXPECT_SECOND_ORDER[0]))):
+        # (a backward without a gradient to r -- energy-only training -- is a parameter backward: raw rows)
+        fdp = None
+        if want_bwd:
+            fdp = meta.fdp_pairs
+            if fdp is None:
+                fdp = kernels.rbf_deriv(r, *meta.rbf, rows=meta.pairs[1])
+        meta.pre = kernels.proj_act(fp, fdp, meta.dkv_eff[0], meta.dkv_eff[1], (meta.acts >> 8) & 15,
+                                    wp=meta.dkv_split())
+    pkv_all = meta.dkv_proj(fp) if (meta.batched and D and not fep and meta.pre is None) else None
     layers = meta.split(params)
     L = len(layers)
     od = dict(dtype=x.dtype, device=x.device)
@@ -484,14 +506,18 @@ def _forward_layers(meta, x, f, C, u, params, r=None, want_bwd=False):
                                         meta.fep_imgs[l], meta.fep_frag, meta.graph, meta.heads, xa, veca,
                                         flags=meta.flags)
         else:
-            if pkv_all is not None:
-                pkv = pkv_all[:, l * D:(l + 1) * D]
+            flags = meta.flags
+            if meta.pre is not None:  # the activated rows; the raw ones are not kept (acts[l][7] None)
+                pkv, rows = None, meta.pre[0][:, l * D:(l + 1) * D]
+                flags |= nat.ET_PREACT
+            elif pkv_all is not None:
+                pkv = rows = pkv_all[:, l * D:(l + 1) * D]
             else:
-                pkv = meta.dkv_proj(fp, l) if dkv_w is not None else None
-            pk = pkv[:, :H] if meta.hk else None
-            pv = pkv[:, H * int(meta.hk):] if meta.hv else None
+                pkv = rows = meta.dkv_proj(fp, l) if dkv_w is not None else None
+            pk = rows[:, :H] if meta.hk else None
+            pv = rows[:, H * int(meta.hk):] if meta.hv else None
             kernels.et_message_fwd_launch(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], vec, pk, pv, C, u,
-                                          meta.graph, meta.heads, xa, veca, meta.flags, meta.pk_rows)
+                                          meta.graph, meta.heads, xa, veca, flags, meta.pk_rows)
         if nf and l + 1 < len(layers):  # o_proj + the epilogue, one launch (the next LayerNorm: its mix)
             o, x_next, vec_next = _oproj_epi(xa, o_w, o_b, x, vec, vecp, veca, vec_all[l + 1])
             acts.append((x, vec, xn, mean, rstd, qkv, vecp, pkv, xa, o))
@@ -557,10 +583,14 @@ def _backward_layers(meta, gX, gV, f, C, u, params, acts, need_ws, r=None, dr=Fa
     # in-kernel, no projection rows at all
     fused = (dr and meta.fep and not rec and not inj and meta.fep_imgs is not None and FUSED_BWD
              and all(a[7] is None for a in acts[:meta.n_layers]))
+    # the force pass on the forward's pre-activated rows (PREACT): S and D instead of the raw rows and the
+    # second projection; every other backward re-forms the raw rows (_act_pkv)
+    pre = (dr and not fused and not rec and not inj and meta.pre is not None and meta.pre[1] is not None
+           and all(a[7] is None for a in acts[:meta.n_layers]))
     if dr:
         assert has_e and not any(need_ws) and meta.rbf is not None
         g_r = zbuf[4 * E:]
-        if not fused:
+        if not fused and not pre:
             if meta.fdp_pairs is not None and meta.pairs is not None:
                 fdp = meta.fdp_pairs
             else:
@@ -619,15 +649,18 @@ def _backward_layers(meta, gX, gV, f, C, u, params, acts, need_ws, r=None, dr=Fa
         gX = gX + x_top
     for l in reversed(range(meta.n_layers)):
         p = layers[l]
-        x, vec, xn, mean, rstd, qkv, vecp, pkv, xa, o_ = acts[l] if fused else _act_pkv(meta, acts, l, f)
+        x, vec, xn, mean, rstd, qkv, vecp, pkv, xa, o_ = acts[l] if (fused or pre) else _act_pkv(meta, acts, l, f)
         ln_w, ln_b = p[0], p[1]
         vec_w, o_w = p[8], p[9]
         qkv_w, _ = meta.qkv_eff[l]
         dkv_w, _ = meta.dkv_layer(l)
         g_qkv, g_o, g_vecp = g_qkv_all[l], g_o_all[l], g_vecp_all[l]
         gpk = gpv = dpk = dpv = None
-        if dr and not fused:
+        if pre:
+            pkv, dpkv = meta.pre[0][:, l * D:(l + 1) * D], meta.pre[1][:, l * D:(l + 1) * D]
+        elif dr and not fused:
             dpkv = dpkv_all[:, l * D:(l + 1) * D] if meta.batched else meta.dkv_proj(fdp, l, bias=False)
+        if dr and not fused:
             dpk = dpkv[:, :H] if meta.hk else None
             dpv = dpkv[:, H * int(meta.hk):] if meta.hv else None
         if has_e and (not dr or rec):
@@ -653,7 +686,7 @@ def _backward_layers(meta, gX, gV, f, C, u, params, acts, need_ws, r=None, dr=Fa
         if acc and vec is not None:  # the injected vec cotangent's buffer takes the gradient
             g_vec_in = injected("vec", l) if injected("vec", l) is not None else torch.zeros((N, 3, H), **o)
         flags = (nat.ACC_VEC_RESIDUAL | (nat.ACC_EDGE if l < L - 1 else 0) | meta.flags
-                 | (nat.ACC_GRADS if acc else 0))
+                 | (nat.ACC_GRADS if acc else 0) | (nat.ET_PREACT if pre else 0))
         if fused:
             kernels.et_fused_bwd_launch(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], vec, C, u, meta.fep_imgs[l],
                                         meta.fep_frag, graph, meta.heads, g_xa, gV, g_qkv[:, :H], g_qkv[:, H:2 * H],
@@ -1287,6 +1320,7 @@ class _ETStack(Function):
         # (autograd is off inside forward: whether a backward can follow is the caller's grad mode and
         # what the inputs say -- needs_input_grad alone follows requires_grad, also under no_grad)
         want = meta.grad_mode and any(ctx.needs_input_grad)
+        meta.r_grad = bool(r is not None and ctx.needs_input_grad[5])
         x_out, vec_out, acts = _forward_layers(meta, x, f, C, u, params, r=r, want_bwd=want)
         ctx.meta = meta
         ctx.acts = acts

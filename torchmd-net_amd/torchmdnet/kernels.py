@@ -1641,6 +1641,41 @@ def proj(A, W, bias=None, out=None, wp=None, row0=0):
     return gemm_lib(Gemm(A, W, True, bias, out, False))
 
 
+def proj_act(A, dA, W, bias, act, wp=None, row0=0, out=None):
+    """The dk/dv projection with its activation in the GEMM's epilogue (``tmdnet_proj_act_f32``): returns
+    (S, D) with S = act(A @ W.T + bias) and, ``dA`` given, D = act'(A @ W.T + bias) * (dA @ W.T) (else D is
+    None) -- the rows the ET message kernels read under ``nat.ET_PREACT``.  ``act``: the kernels' activation
+    code (ACT_CODES); ``wp`` / ``row0`` as in ``proj``; ``out`` = (S, D) buffers of one row stride.  Returns None,
+    nothing launched, outside the kernel's envelope (``proj``'s x3 envelope: CUDA fp32, K = 32 / 64, N % 16 == 0, 16-byte aligned rows): the caller
+    then runs the raw rows."""
+    M, K = A.shape
+    N = W.shape[0]
+    if not (PROJ == "x3" and A.is_cuda and A.dtype == torch.float32 and A.stride(1) == 1 and M > 0
+            and (bias is None or (bias.is_contiguous() and bias.dtype == torch.float32))
+            and (dA is None or (dA.is_cuda and dA.dtype == torch.float32 and dA.shape == A.shape
+                                and dA.stride(1) == 1 and dA.stride(0) == A.stride(0)))):
+        return None
+    if wp is None:
+        wp, row0 = proj_split(W), 0
+    if wp is None:
+        return None
+    if out is not None:
+        S, D = out
+        if S.stride(1) != 1 or (D is not None and (D.stride(1) != 1 or D.stride(0) != S.stride(0))):
+            return None
+    else:
+        S = torch.empty((M, N), dtype=A.dtype, device=A.device)
+        D = torch.empty((M, N), dtype=A.dtype, device=A.device) if dA is not None else None
+    rc = nat.load().tmdnet_proj_act_f32(M, N, K, A.data_ptr(), None if dA is None else dA.data_ptr(), A.stride(0),
+                                        wp[0, row0:].data_ptr(), wp.shape[1] * K,
+                                        None if bias is None else bias.data_ptr(), int(act), S.data_ptr(),
+                                        None if D is None else D.data_ptr(), S.stride(0), nat.stream(A.device))
+    if rc == GEMM_UNSUPPORTED:
+        return None
+    nat.check(rc, "tmdnet_proj_act_f32")
+    return S, D
+
+
 def wgrad_tn(problems):
     """Weight-gradient GEMMs C (+)= A^T B (+ A2^T B2), sums over the rows, all in one
     ``tmdnet_gemm_tn_f32`` launch (fp32; the library per problem otherwise).  Each problem is a dict:
