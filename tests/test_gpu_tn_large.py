@@ -22,13 +22,11 @@ def _rel(a, b):
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
 
 
-@pytest.mark.parametrize("wsplit", ["kernel", "launch"])
 @pytest.mark.parametrize("K,N", [(32, 128), (128, 256), (256, 384), (384, 256), (96, 160)])
-def test_gemm_x3_epilogue_matches_fp64(K, N, wsplit, monkeypatch):
-    """Both weight-split forms: in-kernel while staged in LDS (tmdnet_gemm_x3w_f32, the default) and the
-    pre-split pieces (tmdnet_gemm_x3_ex_f32); K = 96 exercises a partial K chunk, N = 160 a partial column tile."""
+def test_gemm_x3_epilogue_matches_fp64(K, N):
+    """The weight split by one launch per call into its pre-split pieces (tmdnet_gemm_x3_ex_f32, the only form);
+    K = 96 exercises a partial K chunk, N = 160 a partial column tile."""
     from torchmdnet import kernels
-    monkeypatch.setattr(kernels, "X3_WSPLIT", wsplit)
     g = torch.Generator(device=DEV).manual_seed(K + N)
     M = 20000 + 37  # above GEMM_MAX_ROWS, a partial last row tile
     A = torch.randn(M, K, device=DEV, generator=g)

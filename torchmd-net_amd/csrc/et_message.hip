@@ -1631,19 +1631,13 @@ static int et_launch_k(const Args<T>& A, dim3 g, dim3 b, int nbn, hipStream_t st
 
 template <typename T, int V, int S, int KIND, bool ORD>
 static int et_launch_vs(Args<T> A, hipStream_t st) {
-  // channel groups: split heads across XCDs for large systems (L2 working-set), not for the
-  // destination pass (its per-edge channel sums would need a cross-group combine)
-  // channel groups (CS = 2 / 4) are supported by the kernels but measured neutral (+-1 %) on the
-  // C5 water box (tools/kbench.py), so one group is used.
-  int cs = 1;
-  if (KIND == 1 || KIND == 11 || A.H % (cs * V) || (A.H / cs / V) & (A.H / cs / V - 1) || A.H / cs / V < A.lph ||
-      A.H / cs / V > 64)
-    cs = 1;
-  A.HC = A.H / cs;
-  A.L = A.HC / V;
+  // one channel group: splitting the heads of large systems across XCDs (CS = 2 / 4 in the kernels) measured
+  // neutral (+-1 %) on the C5 water box (tools/kbench.py)
+  A.HC = A.H;
+  A.L = A.H / V;
   if (A.L > 64 || (A.L & (A.L - 1))) return kUnsupported;
   const int nbn = (A.n + (4 / S) - 1) / (4 / S);
-  const dim3 g(nbn * cs), b(256);
+  const dim3 g(nbn), b(256);
   // SiLU / SiLU (the configs' activations) runs kernels with the codes as compile-time constants: the
   // runtime-code form splits every per-edge activation into its own basic block (C2: k_bwd_both
   // 226 -> 264 us, k_fwd 83 -> 90 us per step when it was the only form)
@@ -1666,12 +1660,11 @@ static int et_launch_k(const Args<T>& A, dim3 g, dim3 b, int nbn, hipStream_t st
   else if (KIND == 11) hipLaunchKernelGGL((k_bwd_dst<T, V, S, 1, true, false, GA, true>), g, b, 0, st, A);
   else if (KIND == 12) hipLaunchKernelGGL((k_bwd_src<T, V, S, 1, GA, true>), g, b, 0, st, A);
   else if (KIND == 13) hipLaunchKernelGGL((k_bwd_both<T, V, S, 1, true, false, GA, true>), dim3(2 * nbn), b, 0, st, A);
-  else if (KIND == 8 || KIND == 9) {
+  else if (KIND == 8) {
     // dynamic LDS: the node vectors of the block's 4 / S nodes, or the cross-wave reduction
     const size_t node = (size_t)(4 / S) * 12 * A.H, red = S > 1 ? 4 * 64 * 8 * V : 1;
     const size_t bytes = (node > red ? node : red) * sizeof(T);
-    if (KIND == 8) hipLaunchKernelGGL((k_bwd_merged<T, V, S, 1, GA>), dim3(nbn), b, bytes, st, A);
-    else hipLaunchKernelGGL((k_bwd_merged<T, V, S, 0, GA>), dim3(nbn), b, bytes, st, A);
+    hipLaunchKernelGGL((k_bwd_merged<T, V, S, 1, GA>), dim3(nbn), b, bytes, st, A);
   }
   else hipLaunchKernelGGL((k_bwd_dst<T, V, S, 1, false, true, GA>), g, b, 0, st, A);
   return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
@@ -1802,12 +1795,6 @@ static int bwd(int n, int H, int heads, const int32_t* row_ptr, const int32_t* s
   A.dpk = (const T*)dpk; A.dpv = (const T*)dpv; A.gr = (T*)gr;
   A.acc = acc;
   if ((rc = set_acts(A, acc))) return rc;
-  static const int bwd_v = getenv("TMDNET_ET_BWD_V") ? atoi(getenv("TMDNET_ET_BWD_V")) : 0;  // tuning
-  if (bwd_v && bwd_v < V && H % (32 * bwd_v) == 0 && H / bwd_v <= 64 && (A.d / bwd_v) > 0 &&
-      A.d % bwd_v == 0 && !((A.d / bwd_v) & (A.d / bwd_v - 1))) {
-    V = bwd_v;
-    A.lph = A.d / V;
-  }
   if (acc & TMDNET_ET_V_PLANAR) { A.planar = 1; A.vst = H; }
   const bool dr = gr != nullptr;
   if (dr && ((A.pk && !dpk) || (A.pv && !dpv))) return kBadArgument;
@@ -1822,14 +1809,12 @@ static int bwd(int n, int H, int heads, const int32_t* row_ptr, const int32_t* s
     return et_launch<T, 12, false>(V, A, st);
   }
   const bool ag = !dr && (acc & TMDNET_ACC_GRADS) && (A.pk || A.pv);  // injected projection cotangents
-  // dr mode: both roles in one pass over the rows (k_bwd_merged)
-  // (tuning: TMDNET_ET_MERGED=0 off, 1 stream-prefetching variant, 2 loads per edge in the body).
+  // dr mode: both roles in one pass over the rows (k_bwd_merged, its stream rows prefetched one edge ahead).
   // Large graphs only: C5 2.97 vs 3.38 ms per layer (the two passes); at C2 the two passes in one
   // grid (k_bwd_both, twice the waves at 167 vs 222 VGPRs) win, 51 vs 69 us.
-  static const int merged = getenv("TMDNET_ET_MERGED") ? atoi(getenv("TMDNET_ET_MERGED")) : 1;
   const int merged_min = tune_get(TMDNET_TUNE_ET_MERGED_MIN_NODES);
-  if (dr && merged && n >= merged_min && !(acc & TMDNET_ET_TWO_PASS) && !A.gpk && !A.gpv)
-    return merged == 2 ? et_launch<T, 9, false>(V, A, st) : et_launch<T, 8, false>(V, A, st);
+  if (dr && n >= merged_min && !(acc & TMDNET_ET_TWO_PASS) && !A.gpk && !A.gpv)
+    return et_launch<T, 8, false>(V, A, st);
   if (n < fuse_nodes)
     return dr ? et_launch<T, 5, false>(V, A, st) : ag ? et_launch<T, 6, false>(V, A, st) : et_launch<T, 3, false>(V, A, st);
   rc = dr ? et_launch<T, 4, false>(V, A, st) : ag ? et_launch<T, 7, false>(V, A, st) : et_launch<T, 1, false>(V, A, st);

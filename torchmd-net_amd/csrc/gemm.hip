@@ -528,7 +528,7 @@ __global__ __launch_bounds__(256) void k_tn_reduce_v(GroupTN G, int tiles) {
 // edge pairs), so no MFMA runs on the zero half of a 64-wide tile.  The tile numbering and the partial
 // layout are k_gemm_tn_v's (64 x 64 + 64; with NB = 2 the one column tile is n0 = 0 and the reduction
 // never reads columns >= Nr), so k_tn_reduce_v and the workspace size serve both.
-template <int NW, int NB, bool PIPE>
+template <int NW, int NB>
 __global__ __launch_bounds__(NW * 64) void k_gemm_tn_v2(GroupTN G) {
   constexpr int TN = 16 * NB;
   __shared__ float red[TV][TN + 1];
@@ -616,13 +616,6 @@ __global__ __launch_bounds__(NW * 64) void k_gemm_tn_v2(GroupTN G) {
       }
     };
     f4 a0[4], b0[4], a1[4], b1[4];
-    if constexpr (!PIPE) {
-      for (int kb = lo; kb < hi; kb += 16) {
-        load(kb, a0, b0);
-        mma(a0, b0);
-      }
-      continue;
-    }
     load(lo, a0, b0);
     for (int kb = lo; kb < hi; kb += 32) {
       const bool more = kb + 16 < hi;
@@ -1010,13 +1003,8 @@ struct XArgs {
   float* pre;
   const float* rscale;
   const float* dpre;
-  // WS != 0: the right operand as fp32, split into its three pieces while it is staged in LDS (no separate
-  // split launch, nothing cached that an in-place weight update could leave stale): WS = 1 a [N][K] Linear
-  // weight (C = A W^T), WS = 2 a [K][N] right operand (C = A W); row stride ldw
-  const float* W;
-  int ldw;
 };
-template <int MB, int BN, int PD, int WS = 0>
+template <int MB, int BN, int PD>
 __global__ __launch_bounds__(256) void k_gemm_x3(XArgs P) {
   // K chunk staged per barrier pair: 128 (64 at BN = 128) -> ~52 KB of LDS, 3 workgroups per CU
   constexpr int KC = BN >= 128 ? 64 : 128, LD = KC + 8, NB = BN / 16, SPC = KC / 32;
@@ -1075,76 +1063,21 @@ __global__ __launch_bounds__(256) void k_gemm_x3(XArgs P) {
           const int nks = min(KC, P.K - kc) / 32;
           constexpr int CH = KC / 8, NL = 3 * BN * CH / 256;
           const int ch = nks * 4;  // 16-byte chunks per row of this K chunk
-          if constexpr (WS == 0) {
-            u4 stg[NL];
+          u4 stg[NL];
 #pragma unroll
-            for (int i = 0; i < NL; ++i) {
-              const int c = threadIdx.x + 256 * i;
-              const int p = c / (BN * CH), rc = c % (BN * CH), n = rc / CH, k = (rc % CH) * 8;
-              stg[i] = k < 8 * ch
-                           ? *reinterpret_cast<const u4*>(P.Bp + p * ps + (size_t)min(n0 + n, P.N - 1) * P.K + kc + k)
-                           : u4{0u, 0u, 0u, 0u};
-            }
-            __syncthreads();  // the previous chunk's LDS reads are done
+          for (int i = 0; i < NL; ++i) {
+            const int c = threadIdx.x + 256 * i;
+            const int p = c / (BN * CH), rc = c % (BN * CH), n = rc / CH, k = (rc % CH) * 8;
+            stg[i] = k < 8 * ch
+                         ? *reinterpret_cast<const u4*>(P.Bp + p * ps + (size_t)min(n0 + n, P.N - 1) * P.K + kc + k)
+                         : u4{0u, 0u, 0u, 0u};
+          }
+          __syncthreads();  // the previous chunk's LDS reads are done
 #pragma unroll
-            for (int i = 0; i < NL; ++i) {
-              const int c = threadIdx.x + 256 * i;
-              const int p = c / (BN * CH), rc = c % (BN * CH), n = rc / CH, k = (rc % CH) * 8;
-              *reinterpret_cast<u4*>(&w[p][n][k]) = stg[i];
-            }
-          } else if constexpr (WS == 1) {
-            // 8 consecutive k of one weight row per chunk: two 16-byte loads, split8 -> three 16-byte LDS stores
-            constexpr int NC = BN * CH / 256;
-            float4 lo[NC], hi[NC];
-#pragma unroll
-            for (int i = 0; i < NC; ++i) {
-              const int c = threadIdx.x + 256 * i;
-              const int n = c / CH, k = (c % CH) * 8;
-              if (k < 8 * ch) {
-                const float* r = P.W + (size_t)min(n0 + n, P.N - 1) * P.ldw + kc + k;
-                lo[i] = *reinterpret_cast<const float4*>(r);
-                hi[i] = *reinterpret_cast<const float4*>(r + 4);
-              } else {
-                lo[i] = hi[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-              }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < NC; ++i) {
-              const int c = threadIdx.x + 256 * i;
-              const int n = c / CH, k = (c % CH) * 8;
-              bf8 f[3];
-              split8(lo[i], hi[i], f);
-#pragma unroll
-              for (int p = 0; p < 3; ++p) *reinterpret_cast<bf8*>(&w[p][n][k]) = f[p];
-            }
-          } else {
-            // W [K][N]: 4 consecutive n of one k row per 16-byte load, written transposed (2-byte LDS stores)
-            constexpr int NC = KC * BN / 4 / 256, QN = BN / 4;
-            float4 v[NC];
-#pragma unroll
-            for (int i = 0; i < NC; ++i) {
-              const int c = threadIdx.x + 256 * i;
-              const int k = c / QN, n4 = (c % QN) * 4;
-              v[i] = (k < 32 * nks && n0 + n4 < P.N)
-                         ? *reinterpret_cast<const float4*>(P.W + (size_t)(kc + k) * P.ldw + n0 + n4)
-                         : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < NC; ++i) {
-              const int c = threadIdx.x + 256 * i;
-              const int k = c / QN, n4 = (c % QN) * 4;
-              const float x[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                unsigned h, m, l;
-                split3(x[j], h, m, l);
-                w[0][n4 + j][k] = (unsigned short)(h >> 16);
-                w[1][n4 + j][k] = (unsigned short)(m >> 16);
-                w[2][n4 + j][k] = (unsigned short)(l >> 16);
-              }
-            }
+          for (int i = 0; i < NL; ++i) {
+            const int c = threadIdx.x + 256 * i;
+            const int p = c / (BN * CH), rc = c % (BN * CH), n = rc / CH, k = (rc % CH) * 8;
+            *reinterpret_cast<u4*>(&w[p][n][k]) = stg[i];
           }
           __syncthreads();
         }
@@ -1202,373 +1135,6 @@ __global__ __launch_bounds__(256) void k_gemm_x3(XArgs P) {
 }
 
 }  // namespace proj
-
-// ---------------------------------------------------------------------------------------------------
-// The grouped TN GEMM (C (+)= A^T B [+ A2^T B2], bias = column sums of A) on the bf16 MFMA at fp32
-// accuracy (A/B switch TMDNET_TN_V=4): every operand value is split EXACTLY into three bf16 pieces
-// (proj::split3) and the six products with i + j <= 2 are accumulated in fp32, as tmdnet_proj_f32 does
-// -- 6 bf16 MFMAs per 16 x 16 x 32 block = 2.7x the fp32 MFMA's rate.  Both operands arrive k-major
-// (row k holds every m / n) while an MFMA fragment is 8 consecutive k of one m / n, so each 32-row step
-// goes through LDS: coalesced float4 loads, split in registers, written transposed into three bf16
-// planes per operand; the four waves (2 x 2 over the 64 x 64 tile) read 16-byte fragments.  The next
-// step's rows are loaded before the current step's MFMAs.  Tile numbering, split-K partial layout and
-// epilogue are k_gemm_tn_v's (k_tn_reduce_v sums the partials).  Not for one-hot A (the v kernel).
-// Measured (tools/tn_time.py, C2 training shapes): SLOWER than the fp32-MFMA k_gemm_tn_v -- dk/dv 4096 x 64
-// over 6.6k + 13.2k rows 264 vs 142 us, node weights 259 vs 147 us: the transposed 2-byte LDS stores, the
-// in-register splits and two barriers per 32-row step cost more than the MFMA time they save at these
-// 64-wide outputs.  Kept as the A/B form; the default stays k_gemm_tn_v.
-namespace tnx3 {
-
-using gemm::GroupTN;
-using gemm::ProbTN;
-using gemm::TV;
-using gemm::TV_PART;
-using gemm::TNLoc;
-using gemm::tn_locate;
-using gemm::tn_part;
-using bf8 = __bf16 __attribute__((ext_vector_type(8)));
-using f4 = float __attribute__((ext_vector_type(4)));
-constexpr int KB = 32, LDK = KB + 8;  // rows per step; LDS pitch (bf16) of a transposed row
-
-__global__ __launch_bounds__(256) void k_gemm_tn_x3(GroupTN G) {
-  __shared__ __attribute__((aligned(16))) unsigned short la[3][TV][LDK];
-  __shared__ __attribute__((aligned(16))) unsigned short lb[3][TV][LDK];
-  __shared__ float rsum[16][TV];
-  const TNLoc L = tn_locate(G);
-  const ProbTN& P = G.p[L.pi];
-  const int t = L.t, sk = L.sk;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int m0 = (t / P.tiles_n) * TV, n0 = (t % P.tiles_n) * TV;
-  const bool anyones = P.ones1 || P.ones2;
-  const int Nr = anyones ? P.N - 1 : P.N;
-  const bool do_bias = anyones && (t % P.tiles_n) == 0;
-  const bool gemm = n0 < Nr;
-  // (a device row count shortens both segments: the chunks split the rows actually summed)
-  const int cnt = P.rows ? max(0, *P.rows) : P.K + P.K2;
-  const int K1 = min(P.K, cnt), KT = K1 + min(P.K2, cnt);
-  const int nks = (KT + KB - 1) / KB, cper = (nks + P.S - 1) / P.S;
-  const int c_lo = min(KT, sk * cper * KB), c_hi = min(KT, (sk + 1) * cper * KB);
-  // this thread's two float4 of each 32 x 64 operand tile: row kr[j], columns q4 .. q4 + 3
-  const int q4 = (tid & 15) * 4, kr0 = tid >> 4;  // rows kr0 and kr0 + 16
-  const int ma = m0 + q4, na = n0 + q4;
-  const bool mfull = ma + 3 < P.M, nfull = na + 3 < Nr;
-  f4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-  f4 rs = f4{0.f, 0.f, 0.f, 0.f};
-  for (int seg = 0; seg < 2; ++seg) {
-    const int s0 = seg ? K1 : 0, s1 = seg ? KT : K1;
-    const int lo = max(c_lo, s0), hi = min(c_hi, s1);
-    if (lo >= hi) continue;
-    const float* A = seg ? P.A2 : P.A;
-    const float* B = seg ? P.B2 : P.B;
-    const int lda = seg ? P.lda2 : P.lda, ldb = seg ? P.ldb2 : P.ldb;
-    const bool bias_seg = do_bias && (seg ? P.ones2 : P.ones1);
-    auto load = [&](int kb, f4 (&a)[2], f4 (&b)[2]) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int k = kb + kr0 + 16 * j;
-        const bool kv = k < hi;
-        const size_t ro = (size_t)(kv ? k - s0 : 0);
-        if (kv && mfull) {
-          a[j] = *reinterpret_cast<const f4*>(A + ro * lda + ma);
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) a[j][i] = (kv && ma + i < P.M) ? A[ro * lda + ma + i] : 0.f;
-        }
-        if (!gemm || !B) {
-          b[j] = f4{0.f, 0.f, 0.f, 0.f};
-        } else if (kv && nfull) {
-          b[j] = *reinterpret_cast<const f4*>(B + ro * ldb + na);
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) b[j][i] = (kv && na + i < Nr) ? B[ro * ldb + na + i] : 0.f;
-        }
-      }
-    };
-    // split into the three pieces and store transposed: plane[p][column][row]
-    auto stage = [&](const f4 (&a)[2], const f4 (&b)[2]) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int kr = kr0 + 16 * j;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          unsigned h, m, l;
-          proj::split3(a[j][i], h, m, l);
-          la[0][q4 + i][kr] = (unsigned short)(h >> 16);
-          la[1][q4 + i][kr] = (unsigned short)(m >> 16);
-          la[2][q4 + i][kr] = (unsigned short)(l >> 16);
-          proj::split3(b[j][i], h, m, l);
-          lb[0][q4 + i][kr] = (unsigned short)(h >> 16);
-          lb[1][q4 + i][kr] = (unsigned short)(m >> 16);
-          lb[2][q4 + i][kr] = (unsigned short)(l >> 16);
-        }
-      }
-    };
-    f4 a[2], b[2];
-    load(lo, a, b);
-    for (int kb = lo; kb < hi; kb += KB) {
-      if (bias_seg) rs += a[0] + a[1];
-      __syncthreads();  // the previous step's fragments are read
-      stage(a, b);
-      __syncthreads();
-      if (kb + KB < hi) load(kb + KB, a, b);  // next rows in flight during the MFMAs
-      if (gemm) {
-        bf8 fa[2][3], fb[2][3];
-        const int ko = 8 * (lane >> 4);
-#pragma unroll
-        for (int x = 0; x < 2; ++x)
-#pragma unroll
-          for (int p = 0; p < 3; ++p) {
-            fa[x][p] = *reinterpret_cast<const bf8*>(&la[p][32 * wm + 16 * x + (lane & 15)][ko]);
-            fb[x][p] = *reinterpret_cast<const bf8*>(&lb[p][32 * wn + 16 * x + (lane & 15)][ko]);
-          }
-        constexpr int TA[6] = {2, 1, 0, 1, 0, 0}, TB[6] = {0, 1, 2, 0, 1, 0};  // small terms first
-#pragma unroll
-        for (int q = 0; q < 6; ++q)
-#pragma unroll
-          for (int x = 0; x < 2; ++x)
-#pragma unroll
-            for (int y = 0; y < 2; ++y)
-              acc[x][y] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[x][TA[q]], fb[y][TB[q]], acc[x][y], 0, 0, 0);
-      }
-    }
-  }
-  float* part = tn_part(G, P, t, sk);
-  if (gemm) {  // lane holds C[m = 4 (lane >> 4) + i][n = lane & 15] of each 16 x 16 block
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-      for (int y = 0; y < 2; ++y)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int r = 32 * wm + 16 * x + 4 * (lane >> 4) + i, c = 32 * wn + 16 * y + (lane & 15);
-          const float v = acc[x][y][i];
-          if (part) {
-            part[r * TV + c] = v;
-            continue;
-          }
-          const int m = m0 + r, n = n0 + c;
-          if (m >= P.M || n >= Nr) continue;
-          float* out = P.C + (size_t)m * P.ldc + n;
-          *out = P.beta ? *out + v : v;
-        }
-  } else if (part) {  // a bias-only tile: its partial's GEMM block is zero
-    for (int e = tid; e < TV * TV; e += 256) part[e] = 0.f;
-  }
-  if (do_bias) {  // column sums of A: the 16 row lanes of each column quad, in order
-    *reinterpret_cast<f4*>(&rsum[kr0][q4]) = rs;
-    __syncthreads();
-    if (tid < TV) {
-      float v = 0.f;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) v += rsum[i][tid];
-      if (part) {
-        part[TV * TV + tid] = v;
-      } else {
-        const int m = m0 + tid;
-        if (m < P.M) {
-          float* out = P.Cb ? P.Cb + m : P.C + (size_t)m * P.ldc + (P.N - 1);
-          *out = P.beta ? *out + v : v;
-        }
-      }
-    }
-  }
-}
-
-}  // namespace tnx3
-
-// ---------------------------------------------------------------------------------------------------
-// The grouped TN GEMM on the bf16 MFMA at fp32 accuracy with NO LDS staging (TMDNET_TN_V=5).  The k index
-// of an MFMA is a summation label, so a lane may feed ANY 8 rows as its k group as long as its A and B
-// fragments use the same rows: lane (c, g) loads rows kb + 8g + j (j < 8), A columns m0 + 4c .. + 3 and B
-// columns n0 + 4c .. + 3 as float4 (coalesced 256-byte row segments per 16 lanes), and the 8 values of
-// A column m0 + 4c + mb ARE the lane's fragment of 16 x 16 block mb (MFMA row label c) -- k_gemm_tn_v's
-// label permutation with 8 k per lane instead of one.  Each value is split in registers into its three
-// exact bf16 pieces (proj::split3) and the six piece products with i + j <= 2 run as 16x16x32 bf16 MFMAs:
-// 96 MFMAs of 16 cycles per 32-row step of a 64 x 64 tile against the f32 kernel's 128 of 32.  The split
-// of a step happens before the next step's loads are issued (the raw registers are then free), so the
-// loads fly during the MFMAs.  Tile numbering, split-K partial layout, bias (A's column sums from the raw
-// values) and the cross-wave reduction are k_gemm_tn_v's.  Not for one-hot A.
-namespace tnx3r {
-
-using gemm::GroupTN;
-using gemm::ProbTN;
-using gemm::TV;
-using gemm::TV_PART;
-using gemm::TNLoc;
-using gemm::tn_locate;
-using gemm::tn_part;
-using bf8 = __bf16 __attribute__((ext_vector_type(8)));
-using f4 = float __attribute__((ext_vector_type(4)));
-using u4 = unsigned __attribute__((ext_vector_type(4)));
-constexpr int KS = 32;  // rows per step (4 k groups x 8)
-
-// element i of 8 float4 (rows k .. k + 7 of the lane's group) -> the three bf16 fragments
-__device__ __forceinline__ void split_col(const f4 (&x)[8], int i, bf8 (&f)[3]) {
-  unsigned h[8], m[8], l[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) proj::split3(x[j][i], h[j], m[j], l[j]);
-  u4 H, M, L;
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {  // element 2p in the low half of register p
-    H[p] = (h[2 * p] >> 16) | h[2 * p + 1];
-    M[p] = (m[2 * p] >> 16) | m[2 * p + 1];
-    L[p] = (l[2 * p] >> 16) | l[2 * p + 1];
-  }
-  f[0] = __builtin_bit_cast(bf8, H);
-  f[1] = __builtin_bit_cast(bf8, M);
-  f[2] = __builtin_bit_cast(bf8, L);
-}
-
-template <int NW>
-__global__ __launch_bounds__(NW * 64, 2) void k_gemm_tn_x3r(GroupTN G) {
-  __shared__ float red[NW][TV][TV + 1];
-  __shared__ float redb[NW][TV];
-  const TNLoc L = tn_locate(G);
-  const ProbTN& P = G.p[L.pi];
-  const int t = L.t, sk = L.sk;
-  const int w = threadIdx.x / TMD_WAVE, lane = lane_id();
-  const int c = lane & 15, kg = lane >> 4;
-  const int m0 = (t / P.tiles_n) * TV, n0 = (t % P.tiles_n) * TV;
-  const bool anyones = P.ones1 || P.ones2;
-  const int Nr = anyones ? P.N - 1 : P.N;
-  const bool do_bias = anyones && (t % P.tiles_n) == 0;
-  // (a device row count shortens both segments: the chunks split the rows actually summed)
-  const int cnt = P.rows ? max(0, *P.rows) : P.K + P.K2;
-  const int K1 = min(P.K, cnt), KT = K1 + min(P.K2, cnt);
-  const int nkt = (KT + KS - 1) / KS, cper = (nkt + P.S - 1) / P.S;
-  const int c_lo = min(KT, sk * cper * KS), c_hi = min(KT, (sk + 1) * cper * KS);
-  const int nkb = (c_hi - c_lo + KS - 1) / KS, per = (nkb + NW - 1) / NW;
-  const int k_lo = min(c_hi, c_lo + w * per * KS), k_hi = min(c_hi, c_lo + (w + 1) * per * KS);
-  f4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-  f4 rs = f4{0.f, 0.f, 0.f, 0.f};
-  const int ma = m0 + 4 * c, na = n0 + 4 * c;
-  const bool mfull = ma + 3 < P.M, nfull = na + 3 < Nr;
-  const bool gemm = n0 < Nr;
-  for (int seg = 0; seg < 2; ++seg) {
-    const int s0 = seg ? K1 : 0, s1 = seg ? KT : K1;
-    const int lo = max(k_lo, s0), hi = min(k_hi, s1);
-    if (lo >= hi) continue;
-    const float* A = seg ? P.A2 : P.A;
-    const float* B = seg ? P.B2 : P.B;
-    const int lda = seg ? P.lda2 : P.lda, ldb = seg ? P.ldb2 : P.ldb;
-    const bool bias_seg = do_bias && (seg ? P.ones2 : P.ones1);
-    const bool rb = gemm && B;
-    auto load = [&](int kb, f4 (&a)[8], f4 (&b)[8]) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = kb + 8 * kg + j;
-        const bool kv = k < hi;
-        const size_t ro = (size_t)(kv ? k - s0 : 0);
-        if (kv && mfull) {
-          a[j] = *reinterpret_cast<const f4*>(A + ro * lda + ma);
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) a[j][i] = (kv && ma + i < P.M) ? A[ro * lda + ma + i] : 0.f;
-        }
-        if (!rb) {
-          b[j] = f4{0.f, 0.f, 0.f, 0.f};
-        } else if (kv && nfull) {
-          b[j] = *reinterpret_cast<const f4*>(B + ro * ldb + na);
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) b[j][i] = (kv && na + i < Nr) ? B[ro * ldb + na + i] : 0.f;
-        }
-      }
-    };
-    f4 a[8], b[8];
-    load(lo, a, b);
-    for (int kb = lo; kb < hi; kb += KS) {
-      if (bias_seg) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) rs += a[j];
-      }
-      bf8 fa[4][3], fb[4][3];
-      if (gemm) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          split_col(a, i, fa[i]);
-          split_col(b, i, fb[i]);
-        }
-      }
-      if (kb + KS < hi) load(kb + KS, a, b);  // in flight during this step's MFMAs
-      if (gemm) {
-        constexpr int TA[6] = {2, 1, 0, 1, 0, 0}, TB[6] = {0, 1, 2, 0, 1, 0};  // small terms first
-#pragma unroll
-        for (int q = 0; q < 6; ++q)
-#pragma unroll
-          for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb)
-              acc[mb][nb] =
-                  __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[mb][TA[q]], fb[nb][TB[q]], acc[mb][nb], 0, 0, 0);
-      }
-    }
-  }
-  // C layout of a 16x16 block: lane holds MFMA rows 4 (lane >> 4) + i, column lane & 15 (labels as above)
-#pragma unroll
-  for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) red[w][4 * (4 * kg + i) + mb][4 * c + nb] = acc[mb][nb][i];
-  if (do_bias) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float v = rs[i];
-      v += __shfl_xor(v, 16);
-      v += __shfl_xor(v, 32);
-      rs[i] = v;
-    }
-    if (kg == 0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) redb[w][4 * c + i] = rs[i];
-    }
-  }
-  __syncthreads();
-  float* part = tn_part(G, P, t, sk);
-  for (int e = threadIdx.x; e < TV * TV; e += blockDim.x) {
-    const int r = e >> 6, cc = e & 63;
-    float v = 0.f;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) v += red[i][r][cc];
-    if (part) {
-      part[e] = v;
-      continue;
-    }
-    const int m = m0 + r, n = n0 + cc;
-    if (m >= P.M || n >= Nr) continue;
-    float* out = P.C + (size_t)m * P.ldc + n;
-    if (P.beta) v += *out;
-    *out = v;
-  }
-  if (do_bias) {
-    for (int r = threadIdx.x; r < TV; r += blockDim.x) {
-      float v = 0.f;
-#pragma unroll
-      for (int i = 0; i < NW; ++i) v += redb[i][r];
-      if (part) {
-        part[TV * TV + r] = v;
-        continue;
-      }
-      const int m = m0 + r;
-      if (m >= P.M) continue;
-      float* out = P.Cb ? P.Cb + m : P.C + (size_t)m * P.ldc + (P.N - 1);
-      if (P.beta) v += *out;
-      *out = v;
-    }
-  }
-}
-
-}  // namespace tnx3r
 
 namespace emb {
 constexpr int MAX_TABLES = 4;
@@ -1721,8 +1287,6 @@ static int tn_split(int tiles, int kmax, int target = tn_target()) {
 
 // the 16-byte-load kernel needs every A / B row 16-byte aligned (one-hot A: any)
 static bool tn_vec_ok(const gemm::GroupTN& G) {
-  static const bool off = getenv("TMDNET_TN_SCALAR") != nullptr;  // A/B switch
-  if (off) return false;
   auto al = [](const void* p, int ld) { return !p || ((((uintptr_t)p) & 15) == 0 && ld % 4 == 0); };
   for (int i = 0; i < G.n; ++i) {
     const gemm::ProbTN& P = G.p[i];
@@ -1799,28 +1363,20 @@ static void launch_tn(gemm::GroupTN& G, int tiles, int kmax, float* ws, hipStrea
       const gemm::ProbTN& P = G.p[i];
       narrow = narrow && ((P.ones1 || P.ones2) ? P.N - 1 : P.N) <= 32;
     }
-    // (read per launch: tests compare the forms in one process).  Default: the pipelined 32-column form
-    // for narrow groups (4096 x 32 over 6.6k + 6.6k rows: 80 vs 96 us), k_gemm_tn_v for 64-wide tiles
-    // (the pipelined form at 2 waves per SIMD: 289 vs 210 us on the dk/dv weight gradient, 4096 x 64)
+    // TMDNET_TN_V = 1 / 2 forces k_gemm_tn_v / the pipelined k_gemm_tn_v2 (read per launch: tests compare the
+    // two in one process).  Default: the pipelined 32-column form for narrow groups (4096 x 32 over 6.6k +
+    // 6.6k rows: 80 vs 96 us), k_gemm_tn_v for 64-wide tiles (the pipelined form at 2 waves per SIMD: 289 vs
+    // 210 us on the dk/dv weight gradient, 4096 x 64)
     const char* fe = getenv("TMDNET_TN_V");
     const int form = fe ? atoi(fe) : (narrow ? 2 : 1);
-    bool onehot = false;
-    for (int i = 0; i < G.n; ++i) onehot = onehot || G.p[i].onehot;
-    if (form == 4 && !onehot) {
-      hipLaunchKernelGGL(tnx3::k_gemm_tn_x3, dim3(wgs), dim3(256), 0, st, G);
-    } else if (form == 5 && !onehot) {
-      hipLaunchKernelGGL(tnx3r::k_gemm_tn_x3r<4>, dim3(wgs), dim3(256), 0, st, G);
-    } else if (form == 2 || form == 3) {
-      const bool pipe = form == 2;
+    if (form == 2) {
       if (kmax >= 8192 && G.S == 1) {
-        if (narrow) hipLaunchKernelGGL((gemm::k_gemm_tn_v2<8, 2, true>), dim3(tv), dim3(512), 0, st, G);
-        else hipLaunchKernelGGL((gemm::k_gemm_tn_v2<8, 4, true>), dim3(tv), dim3(512), 0, st, G);
+        if (narrow) hipLaunchKernelGGL((gemm::k_gemm_tn_v2<8, 2>), dim3(tv), dim3(512), 0, st, G);
+        else hipLaunchKernelGGL((gemm::k_gemm_tn_v2<8, 4>), dim3(tv), dim3(512), 0, st, G);
       } else if (narrow) {
-        if (pipe) hipLaunchKernelGGL((gemm::k_gemm_tn_v2<4, 2, true>), dim3(wgs), dim3(256), 0, st, G);
-        else hipLaunchKernelGGL((gemm::k_gemm_tn_v2<4, 2, false>), dim3(wgs), dim3(256), 0, st, G);
+        hipLaunchKernelGGL((gemm::k_gemm_tn_v2<4, 2>), dim3(wgs), dim3(256), 0, st, G);
       } else {
-        if (pipe) hipLaunchKernelGGL((gemm::k_gemm_tn_v2<4, 4, true>), dim3(wgs), dim3(256), 0, st, G);
-        else hipLaunchKernelGGL((gemm::k_gemm_tn_v2<4, 4, false>), dim3(wgs), dim3(256), 0, st, G);
+        hipLaunchKernelGGL((gemm::k_gemm_tn_v2<4, 4>), dim3(wgs), dim3(256), 0, st, G);
       }
     } else if (kmax >= 8192 && G.S == 1) {
       hipLaunchKernelGGL(gemm::k_gemm_tn_v<8>, dim3(tv), dim3(512), 0, st, G);
@@ -1995,29 +1551,20 @@ extern "C" int tmdnet_proj_f32(int M, int N, int K, const void* A, int lda, cons
   if ((K != 32 && K != 64) || N % 16 || lda < K || ldc < N || lda % 4 || ldc % 4 || piece_stride < (long long)N * K)
     return kUnsupported;
   if ((((uintptr_t)A) | ((uintptr_t)Wp) | ((uintptr_t)C) | ((uintptr_t)bias)) & 15) return kUnsupported;
-  static const int mb_env = getenv("TMDNET_PROJ_MB") ? atoi(getenv("TMDNET_PROJ_MB")) : 0;  // tuning
-  static const int bn_env = getenv("TMDNET_PROJ_BN") ? atoi(getenv("TMDNET_PROJ_BN")) : 0;
-  // measured (tools/proj_time.py): C2 [6613 x 64] x [64 x 4096] 38 us at 128 x 64 tiles (library 48);
+  // tiles: 128 x 64, 256 x 128 from 65536 rows (K = 32 has only 64-column tiles).  Measured
+  // (tools/proj_time.py): C2 [6613 x 64] x [64 x 4096] 38 us at 128 x 64 tiles (library 48);
   // C5 [1.36M x 64] x [64 x 512] 0.90 ms at 256 x 128 (library 1.07)
   const bool big = M >= 65536;
-  const int mb_req = mb_env ? mb_env : (big ? 4 : 2), bn_req = bn_env ? bn_env : (big ? 128 : 64);
-  // the tile that is actually instantiated for this K (the grid is derived from it, not from the
-  // request: K = 32 has only 64-column tiles)
-  const int bn = (K == 64 && bn_req >= 128) ? 128 : 64;
-  const int mb = mb_req >= 4 ? 4 : (mb_req >= 2 || bn == 128 || K == 32) ? 2 : 1;
+  const int mb = big ? 4 : 2, bn = (big && K == 64) ? 128 : 64;
   proj::Args P{M, N, lda, ldc, piece_stride, (const float*)A, (const unsigned short*)Wp, (const float*)bias,
                (float*)C};
   const dim3 g((N + bn - 1) / bn, (M + 64 * mb - 1) / (64 * mb));
   hipStream_t st = (hipStream_t)stream;
 #define TMD_PROJ(KS_, MB_, BN_) hipLaunchKernelGGL((proj::k_proj_x3<KS_, MB_, BN_>), g, dim3(256), 0, st, P)
   if (K == 64) {
-    if (bn == 128) {
-      if (mb == 4) TMD_PROJ(2, 4, 128); else TMD_PROJ(2, 2, 128);
-    } else {
-      if (mb == 4) TMD_PROJ(2, 4, 64); else if (mb == 2) TMD_PROJ(2, 2, 64); else TMD_PROJ(2, 1, 64);
-    }
+    if (big) TMD_PROJ(2, 4, 128); else TMD_PROJ(2, 2, 64);
   } else {
-    if (mb == 4) TMD_PROJ(1, 4, 64); else TMD_PROJ(1, 2, 64);
+    if (big) TMD_PROJ(1, 4, 64); else TMD_PROJ(1, 2, 64);
   }
 #undef TMD_PROJ
   return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
@@ -2078,33 +1625,10 @@ extern "C" int tmdnet_gemm_x3_f32(int M, int N, int K, const void* A, int lda, c
 // tmdnet_gemm_x3_f32 with tmdnet_gemm_ex_f32's epilogue: pre (the pre-activation, row stride ldx), act (SiLU),
 // rscale (per-row scale), dpre (times silu'(dpre), row stride ldx) -- the Linear + SiLU stacks of large
 // systems (TensorNet's edge MLP over ~1M pair rows at C5) without separate activation passes.
-static int gemm_x3_launch(int M, int N, int K, const void* A, int lda, const void* Bp, const void* W, int ldw, int ws,
-                          const void* bias, void* C, int ldc, int beta, int act, void* pre, const void* rscale,
-                          const void* dpre, int ldx, void* stream);
-
 extern "C" int tmdnet_gemm_x3_ex_f32(int M, int N, int K, const void* A, int lda, const void* Bp, const void* bias,
                                      void* C, int ldc, int beta, int act, void* pre, const void* rscale,
                                      const void* dpre, int ldx, void* stream) {
-  if (!Bp) return kBadArgument;
-  return gemm_x3_launch(M, N, K, A, lda, Bp, nullptr, 0, 0, bias, C, ldc, beta, act, pre, rscale, dpre, ldx, stream);
-}
-
-// The same with the right operand given as fp32 and split inside the kernel while it is staged in LDS:
-// trans_w = 1: W [N][K] (a Linear weight, C = A W^T); trans_w = 0: W [K][N] (C = A W).  ldw % 4 == 0,
-// W 16-byte aligned.
-extern "C" int tmdnet_gemm_x3w_f32(int M, int N, int K, const void* A, int lda, const void* W, int ldw, int trans_w,
-                                   const void* bias, void* C, int ldc, int beta, int act, void* pre,
-                                   const void* rscale, const void* dpre, int ldx, void* stream) {
-  if (!W) return kBadArgument;
-  if (ldw % 4 || (((uintptr_t)W) & 15) || ldw < (trans_w ? K : N)) return kUnsupported;
-  return gemm_x3_launch(M, N, K, A, lda, nullptr, W, ldw, trans_w ? 1 : 2, bias, C, ldc, beta, act, pre, rscale,
-                        dpre, ldx, stream);
-}
-
-static int gemm_x3_launch(int M, int N, int K, const void* A, int lda, const void* Bp, const void* W, int ldw, int ws,
-                          const void* bias, void* C, int ldc, int beta, int act, void* pre, const void* rscale,
-                          const void* dpre, int ldx, void* stream) {
-  if (M < 0 || N <= 0 || K <= 0 || !A || !C) return kBadArgument;
+  if (M < 0 || N <= 0 || K <= 0 || !A || !Bp || !C) return kBadArgument;
   if (M == 0) return kOk;
   if (K % 32 || N % 16 || lda < K || ldc < N || lda % 4 || ldc % 4) return kUnsupported;
   if ((((uintptr_t)A) | ((uintptr_t)Bp) | ((uintptr_t)C) | ((uintptr_t)bias)) & 15) return kUnsupported;
@@ -2115,7 +1639,7 @@ static int gemm_x3_launch(int M, int N, int K, const void* A, int lda, const voi
   }();
   proj::XArgs P{M, N, K, lda, ldc, beta ? 1 : 0, 0, 0, 0, (const float*)A, (const unsigned short*)Bp,
                 (const float*)bias, (float*)C, act ? 1 : 0, ldx, (float*)pre, (const float*)rscale,
-                (const float*)dpre, (const float*)W, ldw};
+                (const float*)dpre};
   hipStream_t st = (hipStream_t)stream;
   // 64-column tiles for wide outputs (the forward mixes, N = 3H..5H), 128 for the narrow input gradients
   // (N = H: one column tile, A read once); 2 row blocks per wave (128 rows per workgroup).  Wide-form
@@ -2136,18 +1660,7 @@ static int gemm_x3_launch(int M, int N, int K, const void* A, int lda, const voi
   P.ny = (M + 127) / 128;
   P.remap = remap_env && P.nx > 1 && (long long)P.nx * P.ny < (1ll << 31);
   const dim3 g = P.remap ? dim3(P.nx * P.ny) : dim3(P.nx, P.ny);
-#define TMD_X3(WS_)                                                               \
-  if (bn == 64)                                                                   \
-    hipLaunchKernelGGL((proj::k_gemm_x3<2, 64, 1, WS_>), g, dim3(256), 0, st, P);  \
-  else                                                                            \
-    hipLaunchKernelGGL((proj::k_gemm_x3<2, 128, 4, WS_>), g, dim3(256), 0, st, P);
-  if (ws == 1) {
-    TMD_X3(1)
-  } else if (ws == 2) {
-    TMD_X3(2)
-  } else {
-    TMD_X3(0)
-  }
-#undef TMD_X3
+  if (bn == 64) hipLaunchKernelGGL((proj::k_gemm_x3<2, 64, 1>), g, dim3(256), 0, st, P);
+  else hipLaunchKernelGGL((proj::k_gemm_x3<2, 128, 4>), g, dim3(256), 0, st, P);
   return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
 }

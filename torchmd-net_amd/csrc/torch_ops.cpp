@@ -1168,8 +1168,7 @@ bool gemm_x3_into(const GemmP& p) {
   if (!x3_ok(p)) return false;
   const int N = p.N(), K = p.K(), ldb = static_cast<int>(p.B.stride(0));
   void* st = stream_of(p.A);
-  // (a split launch per call, as kernels.X3_WSPLIT = "launch": faster at C5 than the in-kernel split of
-  // tmdnet_gemm_x3w_f32, and nothing cached)
+  // (a split launch per call, as kernels.gemm_x3: nothing cached, so in-place weight updates are seen)
   Tensor bp = at::empty({3, N, K}, p.A.options().dtype(at::kShort));
   int rc = p.trans_b ? tmdnet_proj_split_f32(N, K, p.B.data_ptr(), ldb, bp.data_ptr(), st)
                      : tmdnet_split_t_f32(N, K, p.B.data_ptr(), ldb, bp.data_ptr(), st);

@@ -1444,12 +1444,11 @@ GEMM_UNSUPPORTED = 2
 GEMM_MAX_ROWS = 16384  # the grouped split-K kernel's envelope; above it the x3 GEMM (gemm_x3) takes the rows
 # TMDNET_GEMM_BIG=lib keeps the library GEMM above GEMM_MAX_ROWS (A/B switch)
 GEMM_BIG = os.environ.get("TMDNET_GEMM_BIG", "x3")
-# where the weight's bf16 pieces come from: "launch" = a split launch per call (tmdnet_proj_split_f32 /
-# tmdnet_split_t_f32, ~5 us each; nothing cached, so in-place weight updates are always seen), "kernel" = split
-# inside the GEMM while staged in LDS (tmdnet_gemm_x3w_f32: no split launch, but every workgroup re-splits its
-# weight tile -- measured slower: C5 ET 50.8-51.1 vs 48.3-49.1 ms, C5 TensorNet 35.5 vs 34.2 ms per evaluation,
-# the transposed form's 2-byte LDS scatter and the split VALU work competing with the MFMA chain)
-X3_WSPLIT = os.environ.get("TMDNET_X3_WSPLIT", "launch")
+# The x3 kernel's weight pieces come from a split launch per call (tmdnet_proj_split_f32 / tmdnet_split_t_f32,
+# ~5 us each; nothing cached, so in-place weight updates are always seen).  Splitting inside the GEMM while the
+# weight is staged in LDS (no split launch, but every workgroup re-splits its tile) measured slower -- C5 ET
+# 50.8-51.1 vs 48.3-49.1 ms, C5 TensorNet 35.5 vs 34.2 ms per evaluation: the transposed form's 2-byte LDS scatter
+# and the split VALU work compete with the MFMA chain -- and was removed.
 
 
 # One problem C = beta C + A op(B) + bias, op(B) = B^T for a [N][K] Linear weight (trans_b), B for a [K][N] right
@@ -1538,13 +1537,6 @@ def gemm_x3(A, B, tb, bias, C, beta, act=0, pre=None, rscale=None, dpre=None):
     lib = nat.load()
     st = nat.stream(A.device)
     epi = (int(bool(beta)), int(act), nat.ptr(pre), nat.ptr(rscale), nat.ptr(dpre), 0 if x is None else x.stride(0))
-    if X3_WSPLIT == "kernel":
-        # the weight split inside the GEMM while it is staged in LDS (no split launch, nothing cached)
-        rc = lib.tmdnet_gemm_x3w_f32(M, N, K, A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), int(bool(tb)),
-                                     nat.ptr(bias), C.data_ptr(), C.stride(0), *epi, st)
-        if rc != GEMM_UNSUPPORTED:
-            nat.check(rc, "tmdnet_gemm_x3w_f32")
-            return True
     bp = torch.empty((3, N, K), dtype=torch.int16, device=A.device)
     split = lib.tmdnet_proj_split_f32 if tb else lib.tmdnet_split_t_f32
     rc = split(N, K, B.data_ptr(), B.stride(0), bp.data_ptr(), st)
