@@ -619,6 +619,34 @@ int tmdnet_atom_sum_fwd(int dtype, int n_atoms, int n_mol, const void* x, const 
 int tmdnet_atom_sum_bwd(int dtype, int n_atoms, int n_mol, const void* grad_y, const int64_t* batch,
                         const void* std_, void* grad_x, void* stream);
 
+/* Pair-potential priors (reference priors/zbl.py:46-63, d2.py:163-193, coulomb.py:38-50) over a symmetric
+ * CSR list without self loops:  E_mol = 1/2 sum_{edges e of mol} phi_kind(r_e; a_src, b_src, a_dst, b_dst).
+ * a, b [n_atoms]: per-atom parameters gathered by the caller; c0..c3: unit constants formed in double by the
+ * caller (cast to the kernel's type on entry):
+ *   ZBL      a = Z, b = Z^0.23          phi = c0 a_i a_j / r * f(r c1 (b_i + b_j)) * C(r), C the cosine cutoff
+ *                                       (0, c2), c3 = pi / c2, f the four-exponential ZBL screening function
+ *   D2       a = sqrt(C6), b = R_r      phi = -c0 a_i a_j / R^6 / (1 + exp(-c2 (R / (b_i + b_j) - 1))), R = c1 r
+ *   COULOMB  a = q, b unused (nullable) phi = c0 erf(c2 R) a_i a_j / R, R = c1 r
+ * Slots at or past n_slots that row_ptr names (a capacity-truncated list) are ignored.  The edge pointers may
+ * be NULL when n_slots == 0.
+ *   fwd:  e_atom[i] = 1/2 sum_{row i} phi,  dphi[e] = 1/2 phi'(r_e)  (sum e_atom per molecule with
+ *         tmdnet_atom_sum_fwd, std / mean NULL)
+ *   bwd:  g_r[e] = gy[batch[dst(e)]] * dphi[e] for every slot in [0, n_slots); slots no row references
+ *         (static-capacity padding) get exactly 0
+ *   bwd2: for the cotangent gg [n_slots] of g_r:  d_r[e] = gg[e] gy[mol] 1/2 phi''(r_e) (0 in unreferenced
+ *         slots; phi'' recomputed from r, a, b) and t[i] = sum_{row i} gg[e] dphi[e]  (d_gy = the per-molecule
+ *         sum of t, tmdnet_atom_sum_fwd again) */
+enum { TMDNET_PRIOR_ZBL = 0, TMDNET_PRIOR_D2 = 1, TMDNET_PRIOR_COULOMB = 2 };
+int tmdnet_pair_prior_fwd(int dtype, int kind, int n_atoms, int n_slots, const int32_t* row_ptr,
+                          const int32_t* src, const void* r, const void* a, const void* b, double c0, double c1,
+                          double c2, double c3, void* e_atom, void* dphi, void* stream);
+int tmdnet_pair_prior_bwd(int dtype, int n_atoms, int n_slots, int n_mol, const int32_t* row_ptr,
+                          const int64_t* batch, const void* gy, const void* dphi, void* g_r, void* stream);
+int tmdnet_pair_prior_bwd2(int dtype, int kind, int n_atoms, int n_slots, int n_mol, const int32_t* row_ptr,
+                           const int32_t* src, const int64_t* batch, const void* r, const void* a, const void* b,
+                           double c0, double c1, double c2, double c3, const void* gy, const void* gg,
+                           const void* dphi, void* d_r, void* t, void* stream);
+
 /* Scalar head tail fused with the reduction (output_modules.py:83-105, model.py:263-283):
  *   y[b] = *mean + *std * sum_{n: batch[n] = b} (h[n] . w + *b0),  h [n_atoms][K] (ld_h), n_mol <= 8192
  *   (std / mean / b0: device scalars, NULL = 1 / 0 / 0).  Backward: grad_h[n][k] = *std * grad_y[batch[n]] * w[k]. */

@@ -17,6 +17,7 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib",
 F32, F64 = 0, 1
 NL_BRUTE, NL_SHARED, NL_CELL = 0, 1, 2
 RBF_EXPNORM, RBF_GAUSS = 0, 1
+PRIOR_ZBL, PRIOR_D2, PRIOR_COULOMB = 0, 1, 2
 ACC_VEC_RESIDUAL, ACC_EDGE = 1, 2
 ACC_GRADS = 32
 ET_V_PLANAR = 4
@@ -95,6 +96,9 @@ SIGNATURES = {
     "tmdnet_mlp2_down": (I, [I, I, I, P, I, P, P, P, P]),
     "tmdnet_atom_sum_fwd": (I, [I, I, I, P, P, P, P, P, P]),
     "tmdnet_atom_sum_bwd": (I, [I, I, I, P, P, P, P, P]),
+    "tmdnet_pair_prior_fwd": (I, [I, I, I, I, P, P, P, P, P, D, D, D, D, P, P, P]),
+    "tmdnet_pair_prior_bwd": (I, [I, I, I, I, P, P, P, P, P, P]),
+    "tmdnet_pair_prior_bwd2": (I, [I, I, I, I, I, P, P, P, P, P, P, D, D, D, D, P, P, P, P, P, P]),
     "tmdnet_dot_sum_fwd": (I, [I, I, I, P, I, P, P, I, P, P, P, P, P]),
     "tmdnet_dot_sum_bwd": (I, [I, I, I, P, P, I, P, P, P, P]),
     "tmdnet_dot_sum_fwd_atoms": (I, [I, I, I, P, I, P, P, I, P, P, P, P, P, P]),

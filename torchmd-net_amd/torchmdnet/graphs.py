@@ -10,6 +10,10 @@ whole forward + autograd force pass: ~600 launches become one graph launch.
     gm = GraphedEnergyForces(model, z, pos, batch)      # warm-up + capture
     y, neg_dy = gm(pos_new)                              # copy-in + replay (same z/batch layout)
     gm.check_capacity()                                  # raises if a replay overflowed capacity
+
+Pair priors (ZBL, D2, Coulomb) build a neighbour list of their own: each gets its own static capacity from its
+own warm-up pair count (``prior_capacity`` overrides it for all of them) and its own overflow flag, which
+``check_capacity`` reads besides the representation model's.
 """
 import math
 
@@ -21,8 +25,20 @@ def _distance_modules(model):
     return [m for m in model.modules() if isinstance(m, OptimizedDistance)]
 
 
+def pair_priors(model):
+    """The model's pair-potential priors (ZBL, D2, Coulomb): each builds a neighbour list of its own."""
+    from .priors.pair import PairPrior
+    return [p for p in (getattr(model, "prior_model", None) or []) if isinstance(p, PairPrior)]
+
+
+def refuse_pair_priors(model):
+    if pair_priors(model):
+        raise ValueError("captured training with pair priors (ZBL, D2, Coulomb) is not supported; train "
+                         "eagerly with LNNPStep")
+
+
 class GraphedEnergyForces:
-    def __init__(self, model, z, pos, batch, edge_capacity=None, margin=1.25, warmup=3):
+    def __init__(self, model, z, pos, batch, edge_capacity=None, margin=1.25, warmup=3, prior_capacity=None):
         if not model.derivative:
             raise ValueError("GraphedEnergyForces captures TorchMD_Net(derivative=True)")
         rep = model.representation_model
@@ -41,6 +57,12 @@ class GraphedEnergyForces:
         self.edge_capacity = int(edge_capacity)
         for d in dists:
             d.static_capacity = self.edge_capacity
+        # every pair prior sizes its own list from its own warm-up pair count (same margin and rounding)
+        self.priors = pair_priors(model)
+        for p in self.priors:
+            cap = int(math.ceil(int(p.last_num_pairs) * margin / 256.0) * 256) if prior_capacity is None \
+                else int(prior_capacity)
+            p.static_capacity = max(cap, 256)  # a warm-up without pairs still gets a list to fill
         self.pos.requires_grad_(True)
         try:  # pos is a leaf created outside the capture stream; its AccumulateGrad is never used
             torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
@@ -59,6 +81,7 @@ class GraphedEnergyForces:
         torch.cuda.synchronize(dev)
         # device flag written by every replay (lives in the graph's memory pool)
         self.overflow = rep.distance.last_overflow
+        self.prior_overflows = [(type(p).__name__, p.last_overflow) for p in self.priors]
         self.dists = dists
 
     def __call__(self, pos=None):
@@ -72,7 +95,12 @@ class GraphedEnergyForces:
         """Host check (synchronises): the last replay's neighbour list fit the static capacity."""
         if bool(self.overflow.item()):
             raise RuntimeError(f"neighbour pairs exceed the captured edge capacity {self.edge_capacity}")
+        for name, ov in self.prior_overflows:
+            if bool(ov.item()):
+                raise RuntimeError(f"neighbour pairs of the {name} prior exceed its captured capacity {ov.capacity}")
 
     def release(self):
         for d in self.dists:
             d.static_capacity = None
+        for p in self.priors:
+            p.static_capacity = None

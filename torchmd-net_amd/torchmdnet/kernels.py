@@ -1792,6 +1792,166 @@ def atom_sum(x, batch, n_mol, std, mean):
     return _AtomSum.apply(x.contiguous(), batch, int(n_mol), std, mean)
 
 
+# ----------------------------------------------------------------------------- pair-potential priors
+PAIR_PRIOR_KINDS = {"zbl": nat.PRIOR_ZBL, "d2": nat.PRIOR_D2, "coulomb": nat.PRIOR_COULOMB}
+
+
+def pair_phi_composite(kind, r, ai, aj, bi, bj, c):
+    """Differentiable restatement of phi_kind(r) of csrc/pair_prior.hip (c = the four host constants)."""
+    if kind == "zbl":
+        x = r * (c[1] * (bi + bj))
+        f = (0.1818 * torch.exp(-3.2 * x) + 0.5099 * torch.exp(-0.9423 * x) + 0.2802 * torch.exp(-0.4029 * x)
+             + 0.02817 * torch.exp(-0.2016 * x))
+        cut = 0.5 * (torch.cos(c[3] * r) + 1.0) * (r < c[2])
+        return c[0] * ai * aj * f * cut / r
+    if kind == "d2":
+        R = c[1] * r
+        return -c[0] * ai * aj / R ** 6 / (1.0 + torch.exp(-c[2] * (R / (bi + bj) - 1.0)))
+    R = c[1] * r
+    return c[0] * torch.erf(c[2] * R) * ai * aj / R
+
+
+class _PairSpec:
+    """What the three pair-prior launches share: the CSR list (not the graph object, which holds the
+    positions' autograd history), the per-atom parameters and the host constants."""
+
+    def __init__(self, kind, graph, a, b, consts, batch, n_mol):
+        if kind not in PAIR_PRIOR_KINDS:
+            raise ValueError(f"unknown pair prior kind {kind!r} (zbl, d2, coulomb)")
+        self.kind = kind
+        self.code = PAIR_PRIOR_KINDS[kind]
+        self.row_ptr, self.src, self.dst = graph.row_ptr, graph.src, graph.dst
+        self.n = int(graph.n_nodes)
+        self.a, self.b = a, b
+        c = [float(v) for v in consts]
+        self.c = tuple(c + [0.0] * (4 - len(c)))
+        self.batch = batch
+        self.n_mol = int(n_mol)
+
+
+def _mol_sum(x, batch, n_mol):
+    """Per-molecule sum of a per-atom vector: tmdnet_atom_sum_fwd without std / mean; above its molecule limit
+    index_add, as OutputModel.fused_reduce falls back."""
+    if n_mol > ATOM_SUM_MAX_MOLECULES:
+        return torch.zeros(n_mol, dtype=x.dtype, device=x.device).index_add_(0, batch, x)
+    lib = nat.load()
+    y = torch.empty(n_mol, dtype=x.dtype, device=x.device)
+    rc = lib.tmdnet_atom_sum_fwd(nat.dtype_code(x.dtype), x.shape[0], n_mol, nat.ptr(x), nat.ptr(batch), None, None,
+                                 nat.ptr(y), nat.stream(x.device))
+    nat.check(rc, "tmdnet_atom_sum_fwd")
+    return y
+
+
+class _PairPrior(Function):
+    """(r) -> per-molecule energies 1/2 sum phi(r_e); saves 1/2 phi' per slot for the backward."""
+
+    @staticmethod
+    def forward(ctx, r, spec):
+        lib = nat.load()
+        e_atom = torch.empty(spec.n, dtype=r.dtype, device=r.device)
+        dphi = torch.empty_like(r)
+        rc = lib.tmdnet_pair_prior_fwd(nat.dtype_code(r.dtype), spec.code, spec.n, r.shape[0], nat.ptr(spec.row_ptr),
+                                       nat.ptr(spec.src), nat.ptr(r), nat.ptr(spec.a), nat.ptr(spec.b), *spec.c,
+                                       nat.ptr(e_atom), nat.ptr(dphi), nat.stream(r.device))
+        nat.check(rc, "tmdnet_pair_prior_fwd")
+        ctx.spec = spec
+        ctx.save_for_backward(r, dphi)
+        return _mol_sum(e_atom, spec.batch, spec.n_mol)
+
+    @staticmethod
+    def backward(ctx, gy):
+        r, dphi = ctx.saved_tensors
+        return _PairPriorBwd.apply(gy.contiguous(), r, dphi, ctx.spec), None
+
+
+class _PairPriorBwd(Function):
+    """g_r[e] = gy[mol(e)] * 1/2 phi'(r_e) (0 in padding slots).  dphi is a saved function of r: its
+    dependence on r is this Function's own second order (tmdnet_pair_prior_bwd2), not an autograd input."""
+
+    @staticmethod
+    def forward(ctx, gy, r, dphi, spec):
+        lib = nat.load()
+        g_r = torch.empty_like(r)
+        rc = lib.tmdnet_pair_prior_bwd(nat.dtype_code(r.dtype), spec.n, r.shape[0], spec.n_mol,
+                                       nat.ptr(spec.row_ptr), nat.ptr(spec.batch), nat.ptr(gy), nat.ptr(dphi),
+                                       nat.ptr(g_r), nat.stream(r.device))
+        nat.check(rc, "tmdnet_pair_prior_bwd")
+        ctx.spec = spec
+        ctx.save_for_backward(gy, r, dphi)
+        return g_r
+
+    @staticmethod
+    def backward(ctx, gg):
+        gy, r, dphi = ctx.saved_tensors
+        d_gy, d_r = _PairPriorBwd2.apply(gg.contiguous(), gy, r, dphi, ctx.spec)
+        return d_gy, d_r, None, None
+
+
+def pair_prior_bwd2_composite(spec, gg, gy, r):
+    """Differentiable restatement of tmdnet_pair_prior_bwd2: (d_gy, d_r) = the gradient of
+    <gg, gy[mol] * 1/2 phi'(r)> with respect to (gy, r)."""
+    n = spec.n
+    s, d = spec.src.long(), spec.dst.long()
+    live = (s >= 0) & (s < n) & (d >= 0) & (d < n)
+    s, d = s.clamp(0, n - 1), d.clamp(0, n - 1)
+    mol = spec.batch.index_select(0, d)
+    zero = torch.zeros((), dtype=r.dtype, device=r.device)
+    b = spec.b if spec.b is not None else torch.zeros_like(spec.a)
+    rs = torch.where(live, r, torch.ones_like(r))  # padding slots (r = 0) stay finite and are masked below
+    phi = 0.5 * pair_phi_composite(spec.kind, rs, spec.a[d], spec.a[s], b[d], b[s], spec.c)
+    dphi, = torch.autograd.grad(phi.sum(), rs, create_graph=True)
+    g_r = torch.where(live, gy.index_select(0, mol) * dphi, zero)
+    d_gy, d_r = torch.autograd.grad((gg * g_r).sum(), (gy, r), create_graph=True)
+    return d_gy, d_r
+
+
+class _PairPriorBwd2(Function):
+    """Second order (HIP tmdnet_pair_prior_bwd2); its own backward (third order) differentiates the
+    composite, as _NeighborGeomBwd2 does."""
+
+    @staticmethod
+    def forward(ctx, gg, gy, r, dphi, spec):
+        lib = nat.load()
+        d_r = torch.empty_like(r)
+        t = torch.empty(spec.n, dtype=r.dtype, device=r.device)
+        rc = lib.tmdnet_pair_prior_bwd2(nat.dtype_code(r.dtype), spec.code, spec.n, r.shape[0], spec.n_mol,
+                                        nat.ptr(spec.row_ptr), nat.ptr(spec.src), nat.ptr(spec.batch), nat.ptr(r),
+                                        nat.ptr(spec.a), nat.ptr(spec.b), *spec.c, nat.ptr(gy), nat.ptr(gg),
+                                        nat.ptr(dphi), nat.ptr(d_r), nat.ptr(t), nat.stream(r.device))
+        nat.check(rc, "tmdnet_pair_prior_bwd2")
+        ctx.spec = spec
+        ctx.save_for_backward(gg, gy, r)
+        return _mol_sum(t, spec.batch, spec.n_mol), d_r
+
+    @staticmethod
+    def backward(ctx, g_dgy, g_dr):
+        gg, gy, r = ctx.saved_tensors
+        with torch.enable_grad():
+            ins = tuple(t.detach().requires_grad_(True) for t in (gg, gy, r))
+            outs = pair_prior_bwd2_composite(ctx.spec, *ins)
+            pairs = [(o, go) for o, go in zip(outs, (g_dgy, g_dr)) if go is not None]
+            grads = torch.autograd.grad([o for o, _ in pairs], ins, [go for _, go in pairs], create_graph=True,
+                                        allow_unused=True)
+        return grads[0], grads[1], grads[2], None, None
+
+
+def pair_prior(kind, graph, a, b, consts, batch, n_mol):
+    """Per-molecule energies ``(n_mol,)`` of a pair prior over a symmetric CSR ``graph`` without self loops:
+    ``1/2 sum_edges phi_kind(r; a, b)`` (``kind``: "zbl", "d2", "coulomb"; ``a``, ``b``: per-atom parameters,
+    ``b`` None for Coulomb; ``consts``: up to four host floats, include/tmdnet.h).  Differentiable in
+    ``graph.distances`` only, to second order in HIP and beyond through a torch restatement; from the
+    distances the neighbour op's own backward kernels reach the positions."""
+    r = graph.distances
+    nat.require_gpu(r, "pair_prior")
+    a = a.to(r.dtype).contiguous()
+    b = None if b is None else b.to(r.dtype).contiguous()
+    if a.shape[0] != graph.n_nodes or (b is not None and b.shape[0] != graph.n_nodes):
+        raise RuntimeError("pair_prior: one parameter per atom expected")
+    if b is None and kind != "coulomb":
+        raise RuntimeError(f"pair_prior: kind {kind!r} needs the b parameters")
+    return _PairPrior.apply(r, _PairSpec(kind, graph, a, b, consts, batch.contiguous(), n_mol))
+
+
 def _dot_sum_launch(h, w, b0, batch, n_mol, std, mean):
     """y[b] = mean + std * sum_{batch[n] = b} (h[n] . w + b0), one tmdnet_dot_sum_fwd_atoms launch."""
     y = torch.empty((n_mol, 1), dtype=h.dtype, device=h.device)

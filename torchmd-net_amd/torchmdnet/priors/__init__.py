@@ -1,5 +1,9 @@
-"""Priors on the hot path: Atomref only (D2 / ZBL / Coulomb use torch_cluster, out of scope)."""
+"""Priors on the hot path: Atomref (per-element offsets before the molecular sum) and the pair potentials
+D2, ZBL and Coulomb (added after it), which run on the native neighbour list and csrc/pair_prior.hip."""
 from .atomref import Atomref
 from .base import BasePrior
+from .coulomb import Coulomb
+from .d2 import D2
+from .zbl import ZBL
 
-__all__ = ["Atomref"]
+__all__ = ["Atomref", "D2", "ZBL", "Coulomb"]

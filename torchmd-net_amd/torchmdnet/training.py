@@ -319,8 +319,9 @@ class GraphedTrainStep(LNNPStep):
 
     def __init__(self, model, z, pos, batch, y, neg_dy, margin=1.25, warmup=3, **kw):
         import math
+        from .graphs import _distance_modules, refuse_pair_priors
+        refuse_pair_priors(model)
         super().__init__(model, **kw)
-        from .graphs import _distance_modules
         self.z, self.batch = z.clone(), batch.clone()
         self.pos = pos.detach().clone()
         self.y = y.detach().clone()
@@ -605,6 +606,8 @@ class PaddedGraphedTrainer:
 
     def __init__(self, model, batches, lr=4e-4, weight_decay=0.0, y_weight=1.0, neg_dy_weight=1.0,
                  ema_alpha_y=1.0, ema_alpha_neg_dy=1.0, lr_warmup_steps=0, margin=1.3, warmup=2, group=None):
+        from .graphs import refuse_pair_priors
+        refuse_pair_priors(model)
         self.model, self.batches = model, batches
         self.y_weight, self.neg_dy_weight = float(y_weight), float(neg_dy_weight)
         self.alpha_y, self.alpha_f = float(ema_alpha_y), float(ema_alpha_neg_dy)
