@@ -307,17 +307,26 @@ template <typename T> struct CellGeom {
   int nx, ny, nz;
 };
 
-// reference getCell (neighbors_cuda_cell.cuh:38-55): rect wrap, shift by L/2, divide by cutoff,
-// fold an index equal to the cell count back to 0.
+// One axis of the reference getCell (neighbors_cuda_cell.cuh:38-55): shift the wrapped coordinate by
+// L/2, divide by the cutoff, fold an index equal to the cell count (the partial top cell) back to 0.
+// The reference stops there; the wrap, though, is not confined to [-L/2, L/2): one ulp below a +L/2
+// face (or any image of it) p/L + 0.5 rounds up to the next integer and the wrapped coordinate lands
+// one ulp BELOW -L/2, index -1.  That atom sits at the top face, so it goes to the top cell n - 1
+// (its 3-cell neighbourhood {n-2, n-1, 0} covers it, and cells n-1 and 0, the only ones within a
+// cutoff of the face, both scan n-1).  Every other value -- positions past the box's fp resolution,
+// non-finite ones -- is forced into [0, n) as well: the keys index cstart/cend unchecked.
+template <typename T> __device__ __forceinline__ int cell_axis(T wrapped, T L, T cut, int n) {
+  const T f = floor((wrapped + T(0.5) * L) / cut);
+  if (!(f < T(n))) return 0;
+  return f < T(0) ? n - 1 : (int)f;
+}
+
 template <typename T>
 __device__ __forceinline__ void cell_of(const CellGeom<T>& G, V3<T> p, int& cx, int& cy, int& cz) {
   p = rect_apply(p, G.L);
-  cx = (int)floor((p.x + T(0.5) * G.L.x) / G.cut);
-  cy = (int)floor((p.y + T(0.5) * G.L.y) / G.cut);
-  cz = (int)floor((p.z + T(0.5) * G.L.z) / G.cut);
-  if (cx == G.nx) cx = 0;
-  if (cy == G.ny) cy = 0;
-  if (cz == G.nz) cz = 0;
+  cx = cell_axis(p.x, G.L.x, G.cut, G.nx);
+  cy = cell_axis(p.y, G.L.y, G.cut, G.ny);
+  cz = cell_axis(p.z, G.L.z, G.cut, G.nz);
 }
 
 template <typename T>
