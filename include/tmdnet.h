@@ -478,6 +478,42 @@ int tmdnet_nbr_embed_bwd2(int dtype, int n_nodes, int hidden, const int32_t* row
                           int ld_grad_out, const void* gg_x, const void* gg_w, const void* gg_cut,
                           void* d_grad_out, void* d_x, void* d_w, void* d_cut, void* stream);
 
+/* Continuous-filter convolution of the graph-network model (reference CFConv, models/torchmd_gn.py:236-272)
+ * over the destination-grouped CSR list (row t = the edges e with dst_e = t, s = src_e):
+ *   m[e][f] = h[s][f] * w[e][f] * cutoff[e],   out[t][f] = aggr_{e in row t} m[e][f]
+ *   h [N][filters] (ld_h), w [E][filters] (ld_w) = the filter network's output pre-cutoff, cutoff [E],
+ *   out [N][filters].  aggr: ADD the sum; MEAN the sum / max(deg_t, 1), deg_t the row length clamped to
+ *   max_pairs; MAX the maximum, with the winning edge index in arg [N][filters] (int32; required for MAX,
+ *   ignored otherwise) -- an empty row gives out = 0 and arg = -1, and among equal messages the LOWEST edge
+ *   index wins.  Self loops are ordinary edges; slots beyond row_ptr[N] are never read; w and cutoff need
+ *   not agree on an edge and its reverse.  float32 / float64, any filters >= 1 (lanes own 1-, 2- or 4-wide
+ *   channel groups by divisibility and alignment and loop when filters > 64 groups).  No atomics: results
+ *   are bitwise reproducible. */
+enum { TMDNET_AGGR_ADD = 0, TMDNET_AGGR_MEAN = 1, TMDNET_AGGR_MAX = 2 };
+int tmdnet_cfconv_fwd(int dtype, int aggr, int n_nodes, int filters, const int32_t* row_ptr,
+                      const int32_t* src, int max_pairs, const void* h, int ld_h, const void* w, int ld_w,
+                      const void* cutoff, void* out, int32_t* arg, void* stream);
+/* Backward for grad_out [N][filters] (ld_grad_out, 0 = filters), with sel = 1 (ADD, MEAN) or
+ * arg[t][f] == e (MAX) and scale_t = 1 / max(deg_t, 1) (MEAN) or 1:
+ *   gw[e][f] = sel grad_out[t][f] h[s][f] cutoff[e] scale_t,  gcut[e] = sum_f sel grad_out[t][f] h[s][f] w[e][f] scale_t
+ * (destination pass; every slot < max_pairs written, padding zero) and, gh non-NULL,
+ *   gh[j][f] = sum over the edges e = transpose[e'] leaving j (e' in row j) of sel grad_out[dst_e][f] w[e][f] cutoff[e] scale_dst_e
+ * (source pass; needs the transpose map of a symmetric list: TMDNET_UNSUPPORTED without one). */
+int tmdnet_cfconv_bwd(int dtype, int aggr, int n_nodes, int filters, const int32_t* row_ptr,
+                      const int32_t* src, const int32_t* transpose, int max_pairs, const void* h, int ld_h,
+                      const void* w, int ld_w, const void* cutoff, const int32_t* arg, const void* grad_out,
+                      int ld_grad_out, void* gh, void* gw, void* gcut, void* stream);
+/* Second order (force-matching training): the VJP of (gh, gw, gcut) = tmdnet_cfconv_bwd(...) for cotangents
+ * gg_h [N][filters], gg_w [E][filters], gg_cut [E] (NULL = 0) with respect to grad_out, h, w and the cutoff
+ * (arg and deg_t are piecewise constant); outputs NULL = not wanted; edge outputs are written for every slot
+ * < row_ptr[N] (zeros for an edge whose source index is out of range) and NOT for the padding slots beyond it:
+ * hand in zero-filled d_w / d_cut where padding must read as zero; d_h needs the transpose map. */
+int tmdnet_cfconv_bwd2(int dtype, int aggr, int n_nodes, int filters, const int32_t* row_ptr,
+                       const int32_t* src, const int32_t* transpose, int max_pairs, const void* h, int ld_h,
+                       const void* w, int ld_w, const void* cutoff, const int32_t* arg, const void* grad_out,
+                       int ld_grad_out, const void* gg_h, const void* gg_w, const void* gg_cut,
+                       void* d_grad_out, void* d_h, void* d_w, void* d_cut, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * TensorNet edge kernels (reference models/tensornet.py:287-332).
  * Tensors are COMPACT and component-major, [9][N][H]: per channel the coefficients

@@ -18,6 +18,7 @@ F32, F64 = 0, 1
 NL_BRUTE, NL_SHARED, NL_CELL = 0, 1, 2
 RBF_EXPNORM, RBF_GAUSS = 0, 1
 PRIOR_ZBL, PRIOR_D2, PRIOR_COULOMB = 0, 1, 2
+AGGR_CODES = {"add": 0, "mean": 1, "max": 2}
 ACC_VEC_RESIDUAL, ACC_EDGE = 1, 2
 ACC_GRADS = 32
 ET_V_PLANAR = 4
@@ -78,6 +79,9 @@ SIGNATURES = {
     "tmdnet_nbr_embed_fwd": (I, [I, I, I, P, P, I, P, I, P, I, P, P, I, P, P, P]),
     "tmdnet_nbr_embed_bwd": (I, [I, I, I, P, P, I, P, I, P, I, P, P, I, P, P, P, P]),
     "tmdnet_nbr_embed_bwd2": (I, [I, I, I, P, P, P, I, P, I, P, I, P, P, I, P, P, P, P, P, P, P, P]),
+    "tmdnet_cfconv_fwd": (I, [I, I, I, I, P, P, I, P, I, P, I, P, P, P, P]),
+    "tmdnet_cfconv_bwd": (I, [I, I, I, I, P, P, P, I, P, I, P, I, P, P, P, I, P, P, P, P]),
+    "tmdnet_cfconv_bwd2": (I, [I, I, I, I, P, P, P, I, P, I, P, I, P, P, P, I, P, P, P, P, P, P, P, P]),
     "tmdnet_tn_embed_fwd": (I, [I, I, I, P, P, I, D, P, I, P, P, P, I, P, P, P, P]),
     "tmdnet_tn_embed_bwd": (I, [I, I, I, P, P, I, D, P, I, P, P, P, I, P, P, P, P, P, P, P, P, P]),
     "tmdnet_tn_embed_bwd2": (I, [I, I, I, P, P, I, D, P, I, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P,

@@ -42,6 +42,10 @@ class GraphedEnergyForces:
         if not model.derivative:
             raise ValueError("GraphedEnergyForces captures TorchMD_Net(derivative=True)")
         rep = model.representation_model
+        from .models.wrappers import BaseWrapper
+        if isinstance(rep, BaseWrapper):
+            raise ValueError(f"GraphedEnergyForces cannot capture a wrapped representation model "
+                             f"({type(rep).__name__} reads the molecule count on the host); run it eagerly")
         self.model = model
         dev = pos.device
         self.z = z.clone()

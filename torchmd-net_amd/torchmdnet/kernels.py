@@ -1370,6 +1370,152 @@ def nbr_embed(x, w, C, graph, x_self=None):
                            None if x_self is None else x_self.contiguous())
 
 
+# ----------------------------------------------------------------------------- continuous-filter convolution
+def cfconv_composite(h, w, C, src, dst, n_nodes, aggr, arg=None):
+    """PyTorch restatement of ``cfconv`` (CPU tensors; the third-order fallback): messages
+    ``h[src] * w * C`` aggregated over ``dst`` with ``aggr`` in add / mean / max.  Slots with ``src < 0`` are
+    padding.  ``arg`` ([N, F] edge indices, -1 = empty row): the max evaluated with those winners instead of
+    its own (the kernel's choice where two messages tie within rounding)."""
+    keep = (src >= 0).unsqueeze(1)
+    src, dst = src.clamp(min=0), dst.clamp(min=0)
+    m = h.index_select(0, src) * (w * C.unsqueeze(1))
+    N, nf = n_nodes, h.shape[1]
+    if aggr == "max":
+        if arg is not None:
+            if m.shape[0] == 0:
+                return m.new_zeros((N, nf))
+            return m.gather(0, arg.long().clamp(min=0)) * (arg >= 0).to(m.dtype)
+        m = torch.where(keep, m, m.new_full((), -math.inf))
+        out = m.new_full((N, nf), -math.inf).scatter_reduce(0, dst.unsqueeze(1).expand(-1, nf), m, "amax")
+        return torch.where(out == -math.inf, out.new_zeros(()), out)
+    out = m.new_zeros((N, nf)).index_add(0, dst, m * keep.to(m.dtype))
+    if aggr == "mean":
+        deg = torch.zeros(N, dtype=m.dtype, device=m.device).index_add(0, dst, keep[:, 0].to(m.dtype))
+        out = out / deg.clamp(min=1).unsqueeze(1)
+    return out
+
+
+def _cf_rows(t, width):
+    """Rows the cfconv kernels can read: unit element stride and a row stride of at least the width."""
+    if t.stride(-1) != 1 or t.stride(0) < width:
+        t = t.contiguous()
+    return t
+
+
+def _cf_check(rc, what, tr):
+    if rc == 2 and tr is None:  # TMDNET_UNSUPPORTED: the source pass without a transpose map
+        raise RuntimeError("torchmd-net_amd: neighbour-embedding backward needs a symmetric edge list")
+    nat.check(rc, what)
+
+
+class _CFConv(Function):
+    """(out, arg) = cfconv(h, w, C): the CFConv message + aggregation (reference torchmd_gn.py:261-272) with
+    the cutoff multiply inside; ``arg`` (int32 [N, F]) is the max's winning edge, None otherwise."""
+
+    @staticmethod
+    def forward(ctx, h, w, C, graph, aggr):
+        lib = nat.load()
+        N, nf = h.shape
+        out = torch.empty((N, nf), dtype=h.dtype, device=h.device)
+        arg = torch.empty((N, nf), dtype=torch.int32, device=h.device) if aggr == "max" else None
+        rc = lib.tmdnet_cfconv_fwd(nat.dtype_code(h.dtype), nat.AGGR_CODES[aggr], N, nf, nat.ptr(graph.row_ptr),
+                                   nat.ptr(graph.src), graph.n_edges, nat.ptr(h), _ld(h), nat.ptr(w), _ld(w),
+                                   nat.ptr(C), nat.ptr(out), nat.ptr(arg), nat.stream(h.device))
+        nat.check(rc, "tmdnet_cfconv_fwd")
+        ctx.graph, ctx.aggr = graph, aggr
+        ctx.save_for_backward(h, w, C, arg)
+        if arg is not None:
+            ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, gout, _garg=None):
+        h, w, C, arg = ctx.saved_tensors
+        # the node rows' gradient only when something consumes it
+        want_h = bool(ctx.needs_input_grad[0]) and _will_run(ctx.next_functions[0][0])
+        gh, gw, gC = _CFConvBwd.apply(_cf_rows(gout, h.shape[1]), h, w, C, arg, ctx.graph, ctx.aggr, want_h)
+        return gh, gw, gC, None, None
+
+
+class _CFConvBwd(Function):
+    @staticmethod
+    def forward(ctx, gout, h, w, C, arg, graph, aggr, want_h=True):
+        lib = nat.load()
+        N, nf = h.shape
+        E = graph.n_edges
+        gh = torch.empty((N, nf), dtype=h.dtype, device=h.device) if want_h else None
+        # every slot written by the kernel (padding slots zero): no fill
+        zbuf = torch.empty((E * (nf + 1),), dtype=h.dtype, device=h.device)
+        gw, gC = zbuf[:E * nf].view(E, nf), zbuf[E * nf:]
+        tr = graph.transpose if graph.symmetric else None
+        rc = lib.tmdnet_cfconv_bwd(nat.dtype_code(h.dtype), nat.AGGR_CODES[aggr], N, nf, nat.ptr(graph.row_ptr),
+                                   nat.ptr(graph.src), nat.ptr(tr), E, nat.ptr(h), _ld(h), nat.ptr(w), _ld(w),
+                                   nat.ptr(C), nat.ptr(arg), nat.ptr(gout), gout.stride(0), nat.ptr(gh),
+                                   nat.ptr(gw), nat.ptr(gC), nat.stream(h.device))
+        _cf_check(rc, "tmdnet_cfconv_bwd", tr)
+        ctx.graph, ctx.aggr = graph, aggr
+        ctx.save_for_backward(gout, h, w, C, arg)
+        return gh, gw, gC
+
+    @staticmethod
+    def backward(ctx, ggh, ggw, ggC):
+        gout, h, w, C, arg = ctx.saved_tensors
+        graph, aggr = ctx.graph, ctx.aggr
+        _create = torch.is_grad_enabled()  # third order only if the caller builds a graph
+        if not _create and HEAD_SECOND_ORDER != "composite":
+            nodes = [e[0] for e in ctx.next_functions]  # the tensor inputs first: gout, h, w, C
+            want = [bool(ctx.needs_input_grad[i]) and _will_run(nodes[i]) for i in range(4)]
+            if not any(want):
+                return (None,) * 8
+            N, nf = h.shape
+            E = graph.n_edges
+            d_go = torch.empty((N, nf), dtype=h.dtype, device=h.device) if want[0] else None
+            d_h = torch.empty((N, nf), dtype=h.dtype, device=h.device) if want[1] else None
+            # edge outputs: the static-capacity padding slots stay zero (one zero-filled buffer)
+            zb = graph.alloc_edge_grad((E * (nf + 1),), h.dtype, h.device) if (want[2] or want[3]) else None
+            d_w = zb[:E * nf].view(E, nf) if want[2] else None
+            d_C = zb[E * nf:] if want[3] else None
+            tr = graph.transpose if graph.symmetric else None
+            lib = nat.load()
+            rc = lib.tmdnet_cfconv_bwd2(
+                nat.dtype_code(h.dtype), nat.AGGR_CODES[aggr], N, nf, nat.ptr(graph.row_ptr), nat.ptr(graph.src),
+                nat.ptr(tr), E, nat.ptr(h), _ld(h), nat.ptr(w), _ld(w), nat.ptr(C), nat.ptr(arg), nat.ptr(gout),
+                gout.stride(0), nat.ptr(None if ggh is None else ggh.contiguous()),
+                nat.ptr(None if ggw is None else ggw.contiguous()),
+                nat.ptr(None if ggC is None else ggC.contiguous()), nat.ptr(d_go), nat.ptr(d_h), nat.ptr(d_w),
+                nat.ptr(d_C), nat.stream(h.device))
+            _cf_check(rc, "tmdnet_cfconv_bwd2", tr)
+            return d_go, d_h, d_w, d_C, None, None, None, None
+        src, dst = graph.src.long(), graph.dst.long()
+        with torch.enable_grad():
+            leaves = [t.detach().requires_grad_(True) for t in (gout, h, w, C)]
+            go, h_, w_, C_ = leaves
+            out = cfconv_composite(h_, w_, C_, src, dst, graph.n_nodes, aggr, arg=arg)
+            first = torch.autograd.grad(out, (h_, w_, C_), go, create_graph=True)
+            sel = [(f, g) for f, g in zip(first, (ggh, ggw, ggC)) if g is not None]
+            if not sel:
+                return (None,) * 8
+            second = torch.autograd.grad([f for f, _ in sel], leaves, [g for _, g in sel],
+                                         create_graph=_create, allow_unused=True)
+        return tuple(second) + (None, None, None, None)
+
+
+def cfconv(h, w, C, graph, aggr="add", return_arg=False):
+    """Continuous-filter convolution over the CSR ``graph``: ``out[t] = aggr_{e in row t} h[src_e] * w[e] *
+    C[e]`` with ``aggr`` in add / mean / max (mean divides by the row length, at least 1; an empty row's max
+    is 0; equal messages: the lowest edge index wins).  ``w`` is the filter network's output BEFORE the cutoff.
+    GPU tensors run ``tmdnet_cfconv_*`` (forward, backward and second order); CPU tensors the composite.
+    ``return_arg``: also the max's winning edge per (atom, channel) (int32, -1 = empty row; None otherwise)."""
+    if aggr not in nat.AGGR_CODES:
+        raise ValueError(f'cfconv: aggr must be one of "add", "mean", "max" (got {aggr!r})')
+    if not h.is_cuda:
+        out = cfconv_composite(h, w, C, graph.src.long(), graph.dst.long(), graph.n_nodes, aggr)
+        return (out, None) if return_arg else out
+    nf = h.shape[1]
+    out, arg = _CFConv.apply(_cf_rows(h, nf), _cf_rows(w, nf), C.contiguous(), graph, aggr)
+    return (out, arg) if return_arg else out
+
+
 # ----------------------------------------------------------------------------- activation
 def silu_launch(x, scale, out):
     lib = nat.load()

@@ -60,13 +60,28 @@ def create_model(args, prior_model=None, mean=None, std=None):
             equivariance_invariance_group=args["equivariance_invariance_group"],
             **shared_args,
         )
-    elif args["model"] in ("graph-network", "transformer"):
-        raise NotImplementedError(f'{args["model"]} is outside the MI355X hot path (ET, TensorNet)')
+    elif args["model"] == "graph-network":
+        from .torchmd_gn import TorchMD_GN
+
+        is_equivariant = False
+        representation_model = TorchMD_GN(
+            num_filters=args["embedding_dimension"],
+            aggr=args["aggr"],
+            neighbor_embedding=args["neighbor_embedding"],
+            **shared_args,
+        )
+    elif args["model"] == "transformer":
+        raise NotImplementedError(f'{args["model"]} is outside the MI355X hot path (ET, TensorNet, graph-network)')
     else:
         raise ValueError(f'Unknown architecture: {args["model"]}')
 
+    # atom filter (reference model.py:88-92): the wrapped model runs eagerly (models/wrappers.py)
     if args.get("atom_filter", -1) > -1:
-        raise NotImplementedError("AtomFilter wrapper is outside the hot path")
+        if args["derivative"]:
+            raise ValueError("Derivative and atom filter can't be used together")
+        from .wrappers import AtomFilter
+
+        representation_model = AtomFilter(representation_model, args["atom_filter"])
 
     if args.get("prior_model") and prior_model is None:
         prior_model = create_prior_models(args)

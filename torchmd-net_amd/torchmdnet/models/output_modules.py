@@ -123,6 +123,8 @@ class Scalar(OutputModel):
         with `x * std`, the per-molecule sum and `+ mean` (kernels.dot_sum): 2 launches (their backward 2)
         instead of two library GEMMs, the activation, the reduction and their backward passes."""
         net = self.output_network
+        if type(self).pre_reduce is not Scalar.pre_reduce:  # a subclass with its own per-atom term (DipoleMoment)
+            return None
         if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and isinstance(net[1], nn.SiLU)
                 and self.reduce_op in ("sum", "add") and batch.dtype == torch.int64 and std is not None
                 and mean is not None and std.numel() == 1 and mean.numel() == 1

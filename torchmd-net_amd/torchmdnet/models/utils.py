@@ -391,12 +391,11 @@ dtype_mapping = {16: torch.float16, 32: torch.float, 64: torch.float64}
 
 
 class Distance(nn.Module):
-    """torch_cluster radius_graph wrapper of the reference (utils.py:393-453) -- used only by the
-    Graph-Network / Transformer models, which are outside this package's scope."""
+    """torch_cluster radius_graph wrapper of the reference (utils.py:393-453).  Not provided: the graph network
+    and the pair priors take the same pairs from OptimizedDistance (loop=False drops r < cutoff_lower too)."""
 
     def __init__(self, *args, **kwargs):
-        raise NotImplementedError("Distance (torch_cluster) is not part of the ET/TensorNet hot path; "
-                                  "use OptimizedDistance")
+        raise NotImplementedError("Distance (torch_cluster) is not part of this package; use OptimizedDistance")
 
 
 def check_stream_capturing():
