@@ -94,6 +94,16 @@ int tmdnet_nl_build_paired(int dtype, int strategy, const void* pos, const int64
                            void* distances, int32_t* num_pairs, int32_t* row_ptr, int32_t* transpose_map,
                            int pad_output, void* workspace, size_t workspace_bytes, int32_t* pair_row,
                            int32_t* pair_edge, int n_pair_slots, void* stream);
+/* tmdnet_nl_build_paired that also leaves the number of pair rows on the device: num_pair_rows[0] (int32,
+ * nullable) = the number of canonical edges the kept list holds, at most n_pair_slots -- every pair_row
+ * of a kept edge is below it, so a consumer of the pair rows (tmdnet_proj_rows_f32) can stop there.
+ * Written by the row scan: no extra launch, no host sync. */
+int tmdnet_nl_build_paired_rows(int dtype, int strategy, const void* pos, const int64_t* batch, int n_atoms,
+                                const double* box9, int use_periodic, double cutoff_lower, double cutoff_upper,
+                                int max_pairs, int loop, int include_transpose, int32_t* neighbors, void* deltas,
+                                void* distances, int32_t* num_pairs, int32_t* row_ptr, int32_t* transpose_map,
+                                int pad_output, void* workspace, size_t workspace_bytes, int32_t* pair_row,
+                                int32_t* pair_edge, int n_pair_slots, int32_t* num_pair_rows, void* stream);
 
 /* Backward of the neighbour op w.r.t. positions (reference NeighborAutograd::backward,
  * neighbors_cuda.cu:43-71) as a segmented CSR reduction (no atomics, deterministic):
@@ -731,6 +741,12 @@ int tmdnet_pair_index(int n_nodes, const int32_t* row_ptr, const int32_t* src, c
                       const int32_t* transpose, int max_pairs, const int32_t* num_pairs, int sorted_rows,
                       int32_t* pair_row, int32_t* pair_edge, int n_pair_slots, void* workspace,
                       size_t workspace_bytes, void* stream);
+/* tmdnet_pair_index that also writes num_pair_rows[0] (int32 on the device, nullable) = the number of pairs
+ * numbered, at most n_pair_slots (the same number tmdnet_nl_build_paired_rows leaves), from its scan launch. */
+int tmdnet_pair_index_rows(int n_nodes, const int32_t* row_ptr, const int32_t* src, const int32_t* dst,
+                           const int32_t* transpose, int max_pairs, const int32_t* num_pairs, int sorted_rows,
+                           int32_t* pair_row, int32_t* pair_edge, int n_pair_slots, int32_t* num_pair_rows,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* Grouped small fp32 GEMM on the f32 MFMA (node feature mixes of the ET layer, torchmd_et.py:272-312):
  * up to 4 independent problems in one launch.  Problem i: dims[8i..8i+7] = {M, N, K, lda, ldb, ldc,
@@ -829,6 +845,17 @@ int tmdnet_proj_f32(int M, int N, int K, const void* A, int lda, const void* Wp,
 int tmdnet_proj_act_f32(int M, int N, int K, const void* A, const void* dA, int lda, const void* Wp,
                         long long piece_stride, const void* bias, int act, void* S, void* D, int ldc,
                         void* stream);
+/* The two projections over the live rows of a static-capacity buffer: rows (int32 on the device, 4-byte
+ * aligned, nullable) holds the row count, read by the kernel -- no host sync, so a captured step follows the
+ * count of each replay.  It takes effect as min(M, max(0, *rows)).  Rows below it are bit-identical to the
+ * launch without rows; ROWS AT OR PAST IT ARE NOT WRITTEN (C / S / D keep whatever the buffer held), so every
+ * reader must be index-driven or row-counted itself.  Row tiles past the count leave without a store or an
+ * MFMA.  rows NULL: tmdnet_proj_f32 / tmdnet_proj_act_f32.  Same argument checks and return codes. */
+int tmdnet_proj_rows_f32(int M, int N, int K, const void* A, int lda, const void* Wp, long long piece_stride,
+                         const void* bias, void* C, int ldc, const int32_t* rows, void* stream);
+int tmdnet_proj_act_rows_f32(int M, int N, int K, const void* A, const void* dA, int lda, const void* Wp,
+                             long long piece_stride, const void* bias, int act, void* S, void* D, int ldc,
+                             const int32_t* rows, void* stream);
 
 /* The ET message with the dk/dv projection FUSED in (reference torchmd_et.py:282-291 + :314-347, the
  * RBF of models/utils.py:272-344): tmdnet_et_message_fwd's outputs without the projection rows.  Per

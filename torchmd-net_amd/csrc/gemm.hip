@@ -713,7 +713,11 @@ struct Args {
   const unsigned short* Wp;
   const float* bias;
   float* C;
+  const int* rows;         // device row count (NULL: M): rows at or past min(M, max(0, *rows)) are not written
 };
+
+// the live row count of a launch: M, or the device count clamped to [0, M] (a wave-uniform scalar load)
+__device__ __forceinline__ int live_rows(const int* rows, int M) { return rows ? min(M, max(0, *rows)) : M; }
 
 // the three truncated bf16 pieces of x, as fp32 bit patterns with the low half zero
 __device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsigned& l) {
@@ -777,6 +781,7 @@ __global__ __launch_bounds__(256) void k_proj_x3(Args P) {
   const int m0 = (blockIdx.y * 4 + wave) * (16 * MB);
   const int nr = min(BN, P.N - n0);
   const int kq = 8 * (lane >> 4);
+  const int Me = live_rows(P.rows, P.M);  // issued with the A rows, first used after the W loads are out
   // A rows first (their latency overlaps the W tile copy): lane holds row m0 + 16 mb + (lane & 15),
   // k = 32 ks + kq + 0..7
   float4 ar[MB][KS][2];
@@ -801,6 +806,8 @@ __global__ __launch_bounds__(256) void k_proj_x3(Args P) {
     if (c < 3 * BN * CH)
       stg[i] = *reinterpret_cast<const u4*>(P.Wp + p * P.pstride + (size_t)min(n0 + n, P.N - 1) * K + k);
   }
+  // a tile past the device row count: the whole workgroup leaves before the split, the LDS copy and the barrier
+  if ((int)blockIdx.y * (64 * MB) >= Me) return;
 #pragma unroll
   for (int i = 0; i < NL; ++i) {
     const int c = threadIdx.x + 256 * i;
@@ -814,7 +821,7 @@ __global__ __launch_bounds__(256) void k_proj_x3(Args P) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) split8(ar[mb][ks][0], ar[mb][ks][1], a[mb][ks]);
   __syncthreads();
-  if (m0 >= P.M) return;  // (after the barrier: every wave took part in the tile copy)
+  if (m0 >= Me) return;  // (after the barrier: every wave took part in the tile copy)
   for (int nb = 0; nb < nr; nb += 16) {
     bf8 b[KS][3];
 #pragma unroll
@@ -839,7 +846,7 @@ __global__ __launch_bounds__(256) void k_proj_x3(Args P) {
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
       const int m = m0 + 16 * mb + (lane & 15);
-      if (m < P.M) *reinterpret_cast<f4*>(P.C + (size_t)m * P.ldc + n0 + nl) = acc[mb] + bv;
+      if (m < Me) *reinterpret_cast<f4*>(P.C + (size_t)m * P.ldc + n0 + nl) = acc[mb] + bv;
     }
   }
 }
@@ -869,6 +876,7 @@ __global__ __launch_bounds__(256) void k_proj_act_x3(ActArgs Q) {
   const int nr = min(BN, P.N - n0);
   const int kq = 8 * (lane >> 4);
   constexpr int ND = DER ? 2 : 1;  // operand sets: A (and dA)
+  const int Me = live_rows(P.rows, P.M);  // as k_proj_x3
   float4 ar[ND][MB][KS][2];
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb) {
@@ -893,6 +901,7 @@ __global__ __launch_bounds__(256) void k_proj_act_x3(ActArgs Q) {
     if (c < 3 * BN * CH)
       stg[i] = *reinterpret_cast<const u4*>(P.Wp + p * P.pstride + (size_t)min(n0 + n, P.N - 1) * K + k);
   }
+  if ((int)blockIdx.y * (64 * MB) >= Me) return;  // a tile past the device row count (the whole workgroup)
 #pragma unroll
   for (int i = 0; i < NL; ++i) {
     const int c = threadIdx.x + 256 * i;
@@ -908,7 +917,7 @@ __global__ __launch_bounds__(256) void k_proj_act_x3(ActArgs Q) {
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) split8(ar[d][mb][ks][0], ar[d][mb][ks][1], a[d][mb][ks]);
   __syncthreads();
-  if (m0 >= P.M) return;
+  if (m0 >= Me) return;
   const int code = Q.act;
   for (int nb = 0; nb < nr; nb += 16) {
     bf8 b[KS][3];
@@ -954,7 +963,7 @@ __global__ __launch_bounds__(256) void k_proj_act_x3(ActArgs Q) {
           ds[i] = DER ? f.d(pre[i]) : 0.f;
         }
       }
-      if (m < P.M) {
+      if (m < Me) {
         const size_t o = (size_t)m * P.ldc + n0 + nl;
         *reinterpret_cast<f4*>(P.C + o) = s;
         if constexpr (DER) *reinterpret_cast<f4*>(Q.D + o) = ds * acc[1][mb];
@@ -1546,18 +1555,27 @@ extern "C" int tmdnet_proj_split_f32(int N, int K, const void* W, int ldw, void*
 // fp32 in / out on the bf16 MFMA.  K = 32 or 64, N % 16 == 0, 16-byte aligned rows.
 extern "C" int tmdnet_proj_f32(int M, int N, int K, const void* A, int lda, const void* Wp,
                                long long piece_stride, const void* bias, void* C, int ldc, void* stream) {
+  return tmdnet_proj_rows_f32(M, N, K, A, lda, Wp, piece_stride, bias, C, ldc, nullptr, stream);
+}
+
+// tmdnet_proj_f32 stopping at a device row count: rows at or past min(M, max(0, *rows)) are not written
+// (rows NULL: every row).  The rows below it are the bits of the uncounted launch.
+extern "C" int tmdnet_proj_rows_f32(int M, int N, int K, const void* A, int lda, const void* Wp,
+                                    long long piece_stride, const void* bias, void* C, int ldc, const int32_t* rows,
+                                    void* stream) {
   if (M < 0 || N <= 0 || K <= 0 || !A || !Wp || !C) return kBadArgument;
   if (M == 0) return kOk;
   if ((K != 32 && K != 64) || N % 16 || lda < K || ldc < N || lda % 4 || ldc % 4 || piece_stride < (long long)N * K)
     return kUnsupported;
   if ((((uintptr_t)A) | ((uintptr_t)Wp) | ((uintptr_t)C) | ((uintptr_t)bias)) & 15) return kUnsupported;
+  if (((uintptr_t)rows) & 3) return kUnsupported;
   // tiles: 128 x 64, 256 x 128 from 65536 rows (K = 32 has only 64-column tiles).  Measured
   // (tools/proj_time.py): C2 [6613 x 64] x [64 x 4096] 38 us at 128 x 64 tiles (library 48);
   // C5 [1.36M x 64] x [64 x 512] 0.90 ms at 256 x 128 (library 1.07)
   const bool big = M >= 65536;
   const int mb = big ? 4 : 2, bn = (big && K == 64) ? 128 : 64;
   proj::Args P{M, N, lda, ldc, piece_stride, (const float*)A, (const unsigned short*)Wp, (const float*)bias,
-               (float*)C};
+               (float*)C, rows};
   const dim3 g((N + bn - 1) / bn, (M + 64 * mb - 1) / (64 * mb));
   hipStream_t st = (hipStream_t)stream;
 #define TMD_PROJ(KS_, MB_, BN_) hipLaunchKernelGGL((proj::k_proj_x3<KS_, MB_, BN_>), g, dim3(256), 0, st, P)
@@ -1575,6 +1593,14 @@ extern "C" int tmdnet_proj_f32(int M, int N, int K, const void* A, int lda, cons
 extern "C" int tmdnet_proj_act_f32(int M, int N, int K, const void* A, const void* dA, int lda, const void* Wp,
                                    long long piece_stride, const void* bias, int act, void* S, void* D, int ldc,
                                    void* stream) {
+  return tmdnet_proj_act_rows_f32(M, N, K, A, dA, lda, Wp, piece_stride, bias, act, S, D, ldc, nullptr, stream);
+}
+
+// tmdnet_proj_act_f32 stopping at a device row count (as tmdnet_proj_rows_f32): rows of S and D at or past
+// min(M, max(0, *rows)) are not written.
+extern "C" int tmdnet_proj_act_rows_f32(int M, int N, int K, const void* A, const void* dA, int lda, const void* Wp,
+                                        long long piece_stride, const void* bias, int act, void* S, void* D,
+                                        int ldc, const int32_t* rows, void* stream) {
   if (M < 0 || N <= 0 || K <= 0 || !A || !Wp || !S || act < kActSilu || act > kActSigmoid) return kBadArgument;
   if (D && !dA) return kBadArgument;
   if (M == 0) return kOk;
@@ -1582,13 +1608,14 @@ extern "C" int tmdnet_proj_act_f32(int M, int N, int K, const void* A, const voi
     return kUnsupported;
   if ((((uintptr_t)A) | ((uintptr_t)dA) | ((uintptr_t)Wp) | ((uintptr_t)S) | ((uintptr_t)D) | ((uintptr_t)bias)) & 15)
     return kUnsupported;
+  if (((uintptr_t)rows) & 3) return kUnsupported;
   const bool der = D != nullptr;
   // tiles: tmdnet_proj_f32's (128 x 64; 256 x 128 from 65536 rows at K = 64, without the derivative: its
   // second operand and accumulator set double the row registers)
   const bool big = M >= 65536 && K == 64 && !der;
   const int bn = big ? 128 : 64, mb = big ? 4 : 2;
   proj::ActArgs Q{{M, N, lda, ldc, piece_stride, (const float*)A, (const unsigned short*)Wp, (const float*)bias,
-                   (float*)S},
+                   (float*)S, rows},
                   (const float*)dA, (float*)D, act};
   const dim3 g((N + bn - 1) / bn, (M + 64 * mb - 1) / (64 * mb));
   hipStream_t st = (hipStream_t)stream;

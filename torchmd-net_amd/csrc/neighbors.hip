@@ -175,7 +175,9 @@ __global__ __launch_bounds__(256) void k_pairs(Params<T> P, const int* __restric
 // ---------------------------------------------------------------- exclusive scan (one block)
 // counts[0..n) -> row_ptr[0..n], num_pairs[0] = total.  n is at most a few million atoms; one
 // 1024-thread block with per-thread serial chunks is a few microseconds at these sizes.
-// (`ccounts` non-NULL: the canonical counts are scanned the same way into pair_ptr[0..n].)
+// (`ccounts` non-NULL: the canonical counts are scanned the same way into pair_ptr[0..n]; `pair_rows`
+// non-NULL: the canonical edges of the KEPT list -- the rows below the one the capacity `cap` cuts, and its
+// kept part -- clamped to `slots`: the number of pair rows a row-counted consumer walks.)
 __device__ __forceinline__ void block_scan(long long* part, const int* __restrict__ counts, int n,
                                            int* __restrict__ out, int* __restrict__ total) {
   const int tid = threadIdx.x;
@@ -205,12 +207,25 @@ __device__ __forceinline__ void block_scan(long long* part, const int* __restric
 
 __global__ __launch_bounds__(1024) void k_scan(const int* __restrict__ counts, int n, int* __restrict__ row_ptr,
                                                int* __restrict__ num_pairs, const int* __restrict__ ccounts,
-                                               int* __restrict__ pair_ptr) {
+                                               int* __restrict__ pair_ptr, int cap, int slots,
+                                               int* __restrict__ pair_rows) {
   __shared__ long long part[1024];
   block_scan(part, counts, n, row_ptr, num_pairs);
   if (ccounts) {
     __syncthreads();
     block_scan(part, ccounts, n, pair_ptr, nullptr);
+    if (pair_rows) {
+      __syncthreads();  // row_ptr / pair_ptr of the other threads' chunks
+      if (row_ptr[n] <= cap) {
+        if (threadIdx.x == 0) pair_rows[0] = min(pair_ptr[n], slots);
+      } else {  // the one row the capacity cuts: the canonical edges are the row's suffix, the cut takes its tail
+        const int chunk = (n + 1023) / 1024;
+        const int b = threadIdx.x * chunk, e = min(n, b + chunk);
+        for (int i = b; i < e; ++i)
+          if (row_ptr[i] < cap && row_ptr[i + 1] >= cap)
+            pair_rows[0] = min(pair_ptr[i] + max(0, ccounts[i] - (row_ptr[i + 1] - cap)), slots);
+      }
+    }
   }
 }
 
@@ -221,7 +236,9 @@ __global__ __launch_bounds__(1024) void k_scan(const int* __restrict__ counts, i
 // Pair numbering (Pairs::prow non-NULL, sorted rows only; the same numbers as tmdnet_pair_index):
 // the canonical edge of a pair is the direction with src >= dst, numbered row by row in CSR order;
 // in a row sorted by source the canonical edges are its suffix, so edge e's number is closed-form:
-// row r = min(src, dst), k = e if canonical else T(e),  pid = pair_ptr[r] + k - (row_end(r) - cc[r]).
+// row r = min(src, dst), k = e if canonical else T(e),  pid = pair_ptr[r] + k - (row_ptr[r + 1] - cc[r])
+// (the suffix start of the whole row, also where the capacity cuts it: the kept canonical edges of the cut
+// row are the first of its suffix, numbered as tmdnet_pair_index numbers the kept list).
 // Slots past the pair count point at edge 0; a pid outside the slots (capacity-truncated list) reads
 // row 0 and is reported by the capacity check.
 struct Pairs {
@@ -249,7 +266,7 @@ __global__ void k_transpose(int32_t* __restrict__ nb, const int* __restrict__ ro
         const int m = (lo + hi + 1) >> 1;
         if (PR.pair_ptr[m] <= e) lo = m; else hi = m - 1;
       }
-      const int k = e - PR.pair_ptr[lo] + min(row_ptr[lo + 1], cap) - PR.cc[lo];
+      const int k = e - PR.pair_ptr[lo] + row_ptr[lo + 1] - PR.cc[lo];
       edge = (k >= 0 && k < cap) ? k : 0;
     }
     PR.pedge[e] = edge;
@@ -293,7 +310,7 @@ __global__ void k_transpose(int32_t* __restrict__ nb, const int* __restrict__ ro
     const bool canon = s >= t;
     const int r = canon ? t : s, k = canon ? e : found;
     if (s >= 0 && k >= 0) {
-      pid = PR.pair_ptr[r] + k - (min(row_ptr[r + 1], cap) - PR.cc[r]);
+      pid = PR.pair_ptr[r] + k - (row_ptr[r + 1] - PR.cc[r]);
       if (pid < 0 || pid >= PR.slots) pid = 0;
     }
     PR.prow[e] = pid;
@@ -590,7 +607,8 @@ template <typename T>
 static int build(int strategy, const T* pos, const int64_t* batch, int n, const double* box,
                  int periodic, double cl, double cu, int cap, int loop, int transpose, int32_t* nb,
                  T* dlt, T* dist, int32_t* num_pairs, int32_t* row_ptr_out, int32_t* tr, int pad,
-                 char* ws, size_t ws_bytes, int32_t* prow, int32_t* pedge, int slots, hipStream_t st) {
+                 char* ws, size_t ws_bytes, int32_t* prow, int32_t* pedge, int slots, int32_t* pair_rows,
+                 hipStream_t st) {
   if (n <= 0 || cap <= 0 || !(cu > 0)) return kBadArgument;
   if (prow && (!pedge || slots <= 0 || !tr || !transpose || strategy == TMDNET_NL_CELL)) return kBadArgument;
   const Layout Lo = layout(n, strategy, box, cu);
@@ -641,7 +659,8 @@ static int build(int strategy, const T* pos, const int64_t* batch, int n, const 
     hipLaunchKernelGGL(k_cell_bounds, dim3((n + tb - 1) / tb), dim3(tb), 0, st, skeys, n, cstart, cend);
     hipLaunchKernelGGL((k_cell_pairs<T, false>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, P, G, skeys,
                        svals, cstart, cend, counts, row_ptr, cap, nb, dlt, dist);
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, counts, n, row_ptr, num_pairs, nullptr, nullptr);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, counts, n, row_ptr, num_pairs, nullptr, nullptr,
+                       cap, 0, nullptr);
     hipLaunchKernelGGL((k_cell_pairs<T, true>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, P, G, skeys,
                        svals, cstart, cend, counts, row_ptr, cap, nb, dlt, dist);
     if (tr || pad)
@@ -656,7 +675,8 @@ static int build(int strategy, const T* pos, const int64_t* batch, int n, const 
     const int wpb = tb / TMD_WAVE;
     const dim3 g((n + wpb - 1) / wpb);
     hipLaunchKernelGGL((k_pairs<T, false>), g, dim3(tb), 0, st, P, seg, counts, row_ptr, cap, nb, dlt, dist, cc);
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, counts, n, row_ptr, num_pairs, cc, pairp);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, counts, n, row_ptr, num_pairs, cc, pairp, cap,
+                       slots, prow ? pair_rows : nullptr);
     hipLaunchKernelGGL((k_pairs<T, true>), g, dim3(tb), 0, st, P, seg, counts, row_ptr, cap, nb, dlt, dist,
                        nullptr);
     if (tr || pad)
@@ -682,7 +702,7 @@ static int nl_build_any(int dtype, int strategy, const void* pos, const int64_t*
                         int max_pairs, int loop, int include_transpose, int32_t* neighbors, void* deltas,
                         void* distances, int32_t* num_pairs, int32_t* row_ptr, int32_t* transpose_map,
                         int pad_output, void* workspace, size_t workspace_bytes, int32_t* pair_row,
-                        int32_t* pair_edge, int n_pair_slots, void* stream) {
+                        int32_t* pair_edge, int n_pair_slots, int32_t* num_pair_rows, void* stream) {
   if (strategy != TMDNET_NL_BRUTE && strategy != TMDNET_NL_SHARED && strategy != TMDNET_NL_CELL)
     return kBadArgument;
   double unit[9] = {0};
@@ -692,12 +712,12 @@ static int nl_build_any(int dtype, int strategy, const void* pos, const int64_t*
     return nl::build<float>(strategy, (const float*)pos, batch, n_atoms, box, use_periodic, cutoff_lower,
                             cutoff_upper, max_pairs, loop, include_transpose, neighbors, (float*)deltas,
                             (float*)distances, num_pairs, row_ptr, transpose_map, pad_output, (char*)workspace,
-                            workspace_bytes, pair_row, pair_edge, n_pair_slots, st);
+                            workspace_bytes, pair_row, pair_edge, n_pair_slots, num_pair_rows, st);
   if (dtype == TMDNET_F64)
     return nl::build<double>(strategy, (const double*)pos, batch, n_atoms, box, use_periodic, cutoff_lower,
                              cutoff_upper, max_pairs, loop, include_transpose, neighbors, (double*)deltas,
                              (double*)distances, num_pairs, row_ptr, transpose_map, pad_output,
-                             (char*)workspace, workspace_bytes, pair_row, pair_edge, n_pair_slots, st);
+                             (char*)workspace, workspace_bytes, pair_row, pair_edge, n_pair_slots, num_pair_rows, st);
   return kUnsupported;
 }
 
@@ -710,7 +730,7 @@ extern "C" int tmdnet_nl_build(int dtype, int strategy, const void* pos, const i
                                size_t workspace_bytes, void* stream) {
   return nl_build_any(dtype, strategy, pos, batch, n_atoms, box9, use_periodic, cutoff_lower, cutoff_upper,
                       max_pairs, loop, include_transpose, neighbors, deltas, distances, num_pairs, row_ptr,
-                      transpose_map, pad_output, workspace, workspace_bytes, nullptr, nullptr, 0, stream);
+                      transpose_map, pad_output, workspace, workspace_bytes, nullptr, nullptr, 0, nullptr, stream);
 }
 
 extern "C" int tmdnet_nl_build_paired(int dtype, int strategy, const void* pos, const int64_t* batch,
@@ -720,11 +740,25 @@ extern "C" int tmdnet_nl_build_paired(int dtype, int strategy, const void* pos, 
                                       int32_t* row_ptr, int32_t* transpose_map, int pad_output,
                                       void* workspace, size_t workspace_bytes, int32_t* pair_row,
                                       int32_t* pair_edge, int n_pair_slots, void* stream) {
+  return tmdnet_nl_build_paired_rows(dtype, strategy, pos, batch, n_atoms, box9, use_periodic, cutoff_lower,
+                                     cutoff_upper, max_pairs, loop, include_transpose, neighbors, deltas, distances,
+                                     num_pairs, row_ptr, transpose_map, pad_output, workspace, workspace_bytes,
+                                     pair_row, pair_edge, n_pair_slots, nullptr, stream);
+}
+
+extern "C" int tmdnet_nl_build_paired_rows(int dtype, int strategy, const void* pos, const int64_t* batch,
+                                           int n_atoms, const double* box9, int use_periodic, double cutoff_lower,
+                                           double cutoff_upper, int max_pairs, int loop, int include_transpose,
+                                           int32_t* neighbors, void* deltas, void* distances, int32_t* num_pairs,
+                                           int32_t* row_ptr, int32_t* transpose_map, int pad_output,
+                                           void* workspace, size_t workspace_bytes, int32_t* pair_row,
+                                           int32_t* pair_edge, int n_pair_slots, int32_t* num_pair_rows,
+                                           void* stream) {
   if (!pair_row || !pair_edge || n_pair_slots <= 0) return kBadArgument;
   return nl_build_any(dtype, strategy, pos, batch, n_atoms, box9, use_periodic, cutoff_lower, cutoff_upper,
                       max_pairs, loop, include_transpose, neighbors, deltas, distances, num_pairs, row_ptr,
                       transpose_map, pad_output, workspace, workspace_bytes, pair_row, pair_edge, n_pair_slots,
-                      stream);
+                      num_pair_rows, stream);
 }
 
 extern "C" int tmdnet_nl_backward_multi(int dtype, int n_atoms, const int32_t* row_ptr,

@@ -31,6 +31,7 @@ struct P {
   int32_t* pedge;
   int slots;
   int* cnt;  // [n + 1]: canonical count per row, then (in place) its exclusive scan; cnt[n] = total
+  int32_t* nrows;  // (nullable) [1]: min(total, slots), the pair rows a row-counted consumer walks
 };
 
 __device__ __forceinline__ int valid_edges(const P& p) {
@@ -104,7 +105,10 @@ __device__ __forceinline__ void block_scan(const P& p, long long* part) {
     p.cnt[i] = (int)run;
     run += c;
   }
-  if (tid == nt - 1) p.cnt[p.n] = (int)part[nt - 1];
+  if (tid == nt - 1) {
+    p.cnt[p.n] = (int)part[nt - 1];
+    if (p.nrows) p.nrows[0] = (int)min((long long)p.slots, part[nt - 1]);
+  }
 }
 
 __global__ __launch_bounds__(1024) void k_scan(P p) {
@@ -174,13 +178,22 @@ extern "C" int tmdnet_pair_index(int n_nodes, const int32_t* row_ptr, const int3
                                  const int32_t* transpose, int max_pairs, const int32_t* num_pairs,
                                  int sorted_rows, int32_t* pair_row, int32_t* pair_edge, int n_pair_slots,
                                  void* workspace, size_t workspace_bytes, void* stream) {
+  return tmdnet_pair_index_rows(n_nodes, row_ptr, src, dst, transpose, max_pairs, num_pairs, sorted_rows, pair_row,
+                                pair_edge, n_pair_slots, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tmdnet_pair_index_rows(int n_nodes, const int32_t* row_ptr, const int32_t* src, const int32_t* dst,
+                                      const int32_t* transpose, int max_pairs, const int32_t* num_pairs,
+                                      int sorted_rows, int32_t* pair_row, int32_t* pair_edge, int n_pair_slots,
+                                      int32_t* num_pair_rows, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
   if (n_nodes <= 0 || max_pairs < 0 || n_pair_slots < 0 || !row_ptr || !src || !transpose || !pair_row ||
       !pair_edge || (sorted_rows && !dst))
     return kBadArgument;
   if (workspace_bytes < tmdnet_pair_index_workspace_bytes(n_nodes) || !workspace) return kWorkspaceTooSmall;
   hipStream_t st = (hipStream_t)stream;
   pairs::P p{n_nodes, max_pairs, row_ptr, src, dst, transpose, num_pairs, pair_row, pair_edge, n_pair_slots,
-             (int*)workspace};
+             (int*)workspace, num_pair_rows};
   const int m = max(max_pairs, n_pair_slots);
   if (sorted_rows) {
     hipLaunchKernelGGL(pairs::k_count_sorted, dim3((n_nodes + 255) / 256), dim3(256), 0, st, p);

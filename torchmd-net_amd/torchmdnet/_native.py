@@ -39,6 +39,8 @@ SIGNATURES = {
     "tmdnet_nl_workspace_bytes": (SZ, [I, I, P, D]),
     "tmdnet_nl_build": (I, [I, I, P, P, I, P, I, D, D, I, I, I, P, P, P, P, P, P, I, P, SZ, P]),
     "tmdnet_nl_build_paired": (I, [I, I, P, P, I, P, I, D, D, I, I, I, P, P, P, P, P, P, I, P, SZ, P, P, I, P]),
+    "tmdnet_nl_build_paired_rows": (I, [I, I, P, P, I, P, I, D, D, I, I, I, P, P, P, P, P, P, I, P, SZ, P, P, I, P,
+                                        P]),
     "tmdnet_nl_backward": (I, [I, I, P, P, I, P, P, P, P, P, P]),
     "tmdnet_nl_backward_multi": (I, [I, I, P, P, I, P, P, P, P, P, P, P]),
     "tmdnet_nl_backward2": (I, [I, I, P, P, P, I, P, P, P, P, P, P, P, P]),
@@ -56,6 +58,7 @@ SIGNATURES = {
     "tmdnet_rbf_deriv": (I, [I, I, I, P, P, P, D, D, P, I, P, P]),
     "tmdnet_pair_index_workspace_bytes": (SZ, [I]),
     "tmdnet_pair_index": (I, [I, P, P, P, P, I, P, I, P, P, I, P, SZ, P]),
+    "tmdnet_pair_index_rows": (I, [I, P, P, P, P, I, P, I, P, P, I, P, P, SZ, P]),
     "tmdnet_et_message_bwd2": (I, [I, I, I, I, P, P, I, P, I, P, I, P, I, P, P, I, P, I, P, P, P, P,
                                    P, P, P, P, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, P, I, P]),
     "tmdnet_et_message_bwd2_ex": (I, [I, I, I, I, P, P, P, I, P, I, P, I, P, I, P, P, I, P, I, P, P, P, P,
@@ -140,6 +143,8 @@ SIGNATURES = {
     "tmdnet_fep_frags_f32": (I, [ctypes.c_longlong, I, P, P, P, D, D, I, P, P, P]),
     "tmdnet_proj_f32": (I, [I, I, I, P, I, P, ctypes.c_longlong, P, P, I, P]),
     "tmdnet_proj_act_f32": (I, [I, I, I, P, P, I, P, ctypes.c_longlong, P, I, P, P, I, P]),
+    "tmdnet_proj_rows_f32": (I, [I, I, I, P, I, P, ctypes.c_longlong, P, P, I, P, P]),
+    "tmdnet_proj_act_rows_f32": (I, [I, I, I, P, P, I, P, ctypes.c_longlong, P, I, P, P, I, P, P]),
     "tmdnet_mse2_fwd": (I, [I, I, P, P, D, I, P, P, D, P, P]),
     "tmdnet_mse2_bwd": (I, [I, I, P, P, D, I, P, P, D, P, P, P, P]),
     "tmdnet_build_info": (ctypes.c_char_p, []),

@@ -417,6 +417,17 @@ def _pair_f(meta, f):
     return meta.f_pairs if meta.f_pairs is not None else f.index_select(0, meta.pairs[1])
 
 
+def _pair_rows(graph, rows_tensor):
+    """The device pair-row count of a static-capacity graph whose pair slots ``rows_tensor`` holds (CUDA),
+    else None."""
+    npr = getattr(graph, "num_pair_rows_dev", None)
+    pairs = getattr(graph, "_pairs", None)
+    if npr is None or not getattr(graph, "static", False) or pairs is None or not rows_tensor.is_cuda \
+            or rows_tensor.shape[0] != pairs[1].shape[0]:
+        return None
+    return npr
+
+
 def _act_pkv(meta, acts, l, f):
     """Layer l's forward activations, with its projection rows formed now if the fused forward (FEP)
     skipped them (a backward that contracts them: training form, or the unfused dr-mode pass)."""
@@ -458,8 +469,11 @@ def _forward_layers(meta, x, f, C, u, params, r=None, want_bwd=False):
             fdp = meta.fdp_pairs
             if fdp is None:
                 fdp = kernels.rbf_deriv(r, *meta.rbf, rows=meta.pairs[1])
+        # a static-capacity graph: the GEMM stops at the device pair-row count.  S / D are read by the message
+        # kernels alone (forward and the force pass), which walk the CSR and index them through pk_rows --
+        # every row they touch is below the count; the padding rows stay unwritten
         meta.pre = kernels.proj_act(fp, fdp, meta.dkv_eff[0], meta.dkv_eff[1], (meta.acts >> 8) & 15,
-                                    wp=meta.dkv_split())
+                                    wp=meta.dkv_split(), rows=_pair_rows(meta.graph, fp))
     pkv_all = meta.dkv_proj(fp) if (meta.batched and D and not fep and meta.pre is None) else None
     layers = meta.split(params)
     L = len(layers)

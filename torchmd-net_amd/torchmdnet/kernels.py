@@ -96,6 +96,10 @@ class EdgeGraph:
         # zero-filled so padding rows contribute nothing to the weight-gradient GEMMs.
         self.static = static
         self.num_pairs_dev = None
+        # int32 [1] on the device: the number of pair rows of ``pair_index`` (static graphs; written by the
+        # launches that number the pairs).  Every live edge's pair row is below it, so the projection GEMMs
+        # over the pair slots stop there (``proj`` / ``proj_act`` ``rows=``)
+        self.num_pair_rows_dev = None
 
     def alloc_edge_grad(self, shape, dtype, device):
         return (torch.zeros if self.static else torch.empty)(shape, dtype=dtype, device=device)
@@ -146,10 +150,12 @@ _STRATEGY = {"brute": nat.NL_BRUTE, "shared": nat.NL_SHARED, "cell": nat.NL_CELL
 
 
 def neighbor_pairs_raw(strategy, pos, batch, box, use_periodic, cutoff_lower, cutoff_upper,
-                       max_pairs, loop, include_transpose, pad_output=True, want_csr=False, pairs_out=None):
+                       max_pairs, loop, include_transpose, pad_output=True, want_csr=False, pairs_out=None,
+                       pair_rows_out=None):
     """Launch ``tmdnet_nl_build``.  Returns (neighbors, deltas, distances, num_pairs, row_ptr, T).
     ``pairs_out`` = (pair_row [max_pairs], pair_edge [slots]) int32: also number the edge pairs in the
-    same launches (``tmdnet_nl_build_paired``; sorted-row strategies with the transpose map)."""
+    same launches (``tmdnet_nl_build_paired_rows``; sorted-row strategies with the transpose map), with the
+    number of pair rows left in ``pair_rows_out`` (int32 [1], optional)."""
     lib = nat.load()
     nat.require_gpu(pos, "get_neighbor_pairs")
     if strategy not in _STRATEGY:
@@ -194,8 +200,9 @@ def neighbor_pairs_raw(strategy, pos, batch, box, use_periodic, cutoff_lower, cu
         pr, pe = pairs_out
         if tr is None or st == nat.NL_CELL or pr.shape[0] != cap:
             raise RuntimeError("pair numbering in the build needs sorted rows and the transpose map")
-        rc = lib.tmdnet_nl_build_paired(*args, nat.ptr(pr), nat.ptr(pe), pe.shape[0], nat.stream(dev))
-        nat.check(rc, "tmdnet_nl_build_paired")
+        rc = lib.tmdnet_nl_build_paired_rows(*args, nat.ptr(pr), nat.ptr(pe), pe.shape[0], nat.ptr(pair_rows_out),
+                                             nat.stream(dev))
+        nat.check(rc, "tmdnet_nl_build_paired_rows")
     else:
         rc = lib.tmdnet_nl_build(*args, nat.stream(dev))
         nat.check(rc, "tmdnet_nl_build")
@@ -386,9 +393,10 @@ def build_graph(pos, batch, cutoff_lower, cutoff_upper, max_num_pairs, loop=True
                        torch.empty(((c + n) // 2,), dtype=torch.int32, device=pos.device))
     if static_capacity is not None:
         cap = int(static_capacity)
+        nrows = torch.empty((1,), dtype=torch.int32, device=pos.device) if fused_pairs is not None else None
         nb, dl, dist, num, row_ptr, tr = neighbor_pairs_raw(
             strategy, pos, batch, box, use_periodic, cutoff_lower, cutoff_upper, cap, loop,
-            True, pad_output=True, want_csr=True, pairs_out=fused_pairs)
+            True, pad_output=True, want_csr=True, pairs_out=fused_pairs, pair_rows_out=nrows)
         graph = EdgeGraph(pos.shape[0], row_ptr, nb[0], nb[1], tr, None, None, None, symmetric=True,
                           static=True)
         graph.num_pairs_dev = num
@@ -396,6 +404,7 @@ def build_graph(pos, batch, cutoff_lower, cutoff_upper, max_num_pairs, loop=True
         graph.sorted_rows = strategy != "cell"  # brute / shared rows list sources ascending
         if fused_pairs is not None:
             graph._pairs = fused_pairs
+            graph.num_pair_rows_dev = nrows
         deltas, distances, distances2 = _NeighborGeom.apply(pos, graph, dl, dist)
         graph.deltas = deltas
         graph.distances = distances
@@ -861,12 +870,16 @@ def pair_index_launch(graph, pair_row, pair_edge):
     lib = nat.load()
     n = graph.n_nodes
     ws = torch.empty(int(lib.tmdnet_pair_index_workspace_bytes(n)), dtype=torch.uint8, device=pair_row.device)
-    rc = lib.tmdnet_pair_index(n, nat.ptr(graph.row_ptr), nat.ptr(graph.src), nat.ptr(graph.dst),
-                               nat.ptr(graph.transpose), graph.n_edges, nat.ptr(graph.num_pairs_dev),
-                               int(getattr(graph, "sorted_rows", False)), nat.ptr(pair_row),
-                               nat.ptr(pair_edge), pair_edge.shape[0], nat.ptr(ws), ws.numel(),
-                               nat.stream(pair_row.device))
-    nat.check(rc, "tmdnet_pair_index")
+    nrows = None
+    if getattr(graph, "static", False):  # the device pair-row count rides on the scan launch
+        nrows = torch.empty((1,), dtype=torch.int32, device=pair_row.device)
+    rc = lib.tmdnet_pair_index_rows(n, nat.ptr(graph.row_ptr), nat.ptr(graph.src), nat.ptr(graph.dst),
+                                    nat.ptr(graph.transpose), graph.n_edges, nat.ptr(graph.num_pairs_dev),
+                                    int(getattr(graph, "sorted_rows", False)), nat.ptr(pair_row),
+                                    nat.ptr(pair_edge), pair_edge.shape[0], nat.ptr(nrows), nat.ptr(ws), ws.numel(),
+                                    nat.stream(pair_row.device))
+    nat.check(rc, "tmdnet_pair_index_rows")
+    graph.num_pair_rows_dev = nrows
 
 
 def pair_index(graph):
@@ -1756,11 +1769,23 @@ def proj_split(W):
     return wp
 
 
-def proj(A, W, bias=None, out=None, wp=None, row0=0):
+def _rows_ptr(rows, dev):
+    """The pointer of a device row count (int32 [1] on ``dev``) for the row-counted projections, None for None."""
+    if rows is None:
+        return None
+    if rows.dtype != torch.int32 or rows.device != dev or rows.numel() != 1:
+        raise RuntimeError("rows must be one int32 on the operands' device")
+    return rows.data_ptr()
+
+
+def proj(A, W, bias=None, out=None, wp=None, row0=0, *, rows=None):
     """``A @ W.T (+ bias)`` for the dk/dv projection shapes (``tmdnet_proj_f32``: K = 32 / 64, fp32,
     16-byte aligned rows, N % 16 == 0); anything else, fp64 parity runs and ``TMDNET_PROJ=lib`` use
     the library GEMM on the same device.  ``wp``: W's split from ``proj_split`` when the caller shares
-    it between GEMMs (W = rows [row0, row0 + N) of the split weight); ``out`` receives the result."""
+    it between GEMMs (W = rows [row0, row0 + N) of the split weight); ``out`` receives the result.
+    ``rows``: an int32 [1] device row count (``tmdnet_proj_rows_f32``) -- the kernel writes the rows below min(M, max(0, rows)) only,
+    the others keep what the buffer held (every reader must be index-driven or row-counted); the library
+    path computes every row."""
     M, K = A.shape
     N = W.shape[0]
     if out is None:
@@ -1770,17 +1795,22 @@ def proj(A, W, bias=None, out=None, wp=None, row0=0):
         if wp is None:
             wp, row0 = proj_split(W), 0
         if wp is not None:
-            rc = nat.load().tmdnet_proj_f32(M, N, K, A.data_ptr(), A.stride(0), wp[0, row0:].data_ptr(),
-                                            wp.shape[1] * K, None if bias is None else bias.data_ptr(),
-                                            out.data_ptr(), out.stride(0), nat.stream(A.device))
+            args = (M, N, K, A.data_ptr(), A.stride(0), wp[0, row0:].data_ptr(), wp.shape[1] * K,
+                    None if bias is None else bias.data_ptr(), out.data_ptr(), out.stride(0))
+            if rows is None:
+                name, rc = "tmdnet_proj_f32", nat.load().tmdnet_proj_f32(*args, nat.stream(A.device))
+            else:
+                name, rc = "tmdnet_proj_rows_f32", nat.load().tmdnet_proj_rows_f32(
+                    *args, _rows_ptr(rows, A.device), nat.stream(A.device))
             if rc != GEMM_UNSUPPORTED:
-                nat.check(rc, "tmdnet_proj_f32")
+                nat.check(rc, name)
                 return out
     return gemm_lib(Gemm(A, W, True, bias, out, False))
 
 
-def proj_act(A, dA, W, bias, act, wp=None, row0=0, out=None):
-    """The dk/dv projection with its activation in the GEMM's epilogue (``tmdnet_proj_act_f32``): returns
+def proj_act(A, dA, W, bias, act, wp=None, row0=0, out=None, *, rows=None):
+    """The dk/dv projection with its activation in the GEMM's epilogue (``tmdnet_proj_act_f32``; ``rows``
+    as in ``proj``: S and D rows at or past the device count are not written): returns
     (S, D) with S = act(A @ W.T + bias) and, ``dA`` given, D = act'(A @ W.T + bias) * (dA @ W.T) (else D is
     None) -- the rows the ET message kernels read under ``nat.ET_PREACT``.  ``act``: the kernels' activation
     code (ACT_CODES); ``wp`` / ``row0`` as in ``proj``; ``out`` = (S, D) buffers of one row stride.  Returns None,
@@ -1804,13 +1834,17 @@ def proj_act(A, dA, W, bias, act, wp=None, row0=0, out=None):
     else:
         S = torch.empty((M, N), dtype=A.dtype, device=A.device)
         D = torch.empty((M, N), dtype=A.dtype, device=A.device) if dA is not None else None
-    rc = nat.load().tmdnet_proj_act_f32(M, N, K, A.data_ptr(), None if dA is None else dA.data_ptr(), A.stride(0),
-                                        wp[0, row0:].data_ptr(), wp.shape[1] * K,
-                                        None if bias is None else bias.data_ptr(), int(act), S.data_ptr(),
-                                        None if D is None else D.data_ptr(), S.stride(0), nat.stream(A.device))
+    args = (M, N, K, A.data_ptr(), None if dA is None else dA.data_ptr(), A.stride(0), wp[0, row0:].data_ptr(),
+            wp.shape[1] * K, None if bias is None else bias.data_ptr(), int(act), S.data_ptr(),
+            None if D is None else D.data_ptr(), S.stride(0))
+    if rows is None:
+        name, rc = "tmdnet_proj_act_f32", nat.load().tmdnet_proj_act_f32(*args, nat.stream(A.device))
+    else:
+        name, rc = "tmdnet_proj_act_rows_f32", nat.load().tmdnet_proj_act_rows_f32(
+            *args, _rows_ptr(rows, A.device), nat.stream(A.device))
     if rc == GEMM_UNSUPPORTED:
         return None
-    nat.check(rc, "tmdnet_proj_act_f32")
+    nat.check(rc, name)
     return S, D
 
 
