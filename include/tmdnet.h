@@ -524,6 +524,44 @@ int tmdnet_cfconv_bwd2(int dtype, int aggr, int n_nodes, int filters, const int3
                        int ld_grad_out, const void* gg_h, const void* gg_w, const void* gg_cut,
                        void* d_grad_out, void* d_h, void* d_w, void* d_cut, void* stream);
 
+/* Continuous-filter convolution with the filter network evaluated inside the edge kernel (cfconv_fused.hip;
+ * the optimize() path of the graph network, reference optimize.py).  Per edge e of CSR row t (source s,
+ * distance r_e = dist[e], cutoff C_e = cutoff[e]), f = the radial basis of tmdnet_edge_geom_fwd (rbf_type, mu,
+ * beta, cutoff_lower, cutoff_upper as there), act = TMDNET_ACT_SSP or TMDNET_ACT_SILU:
+ *   a_e = act(W1 f(r_e) + b1),  w_e = W2 a_e + b2                 (never written to memory)
+ *   out[t] = scale_t sum_{e in row t} h[s] * w_e * C_e,   scale_t = 1 (ADD) or 1 / max(deg_t, 1) (MEAN)
+ * Weights come as the image of tmdnet_cfconv_fused_image: W1 [filters][num_rbf], b1 [filters], W2
+ * [filters][filters], b2 [filters] of n_layers layers (HOST arrays of n_layers device pointers, contiguous
+ * fp32; b1 / b2 or single entries NULL = zero) split into three exact bf16 pieces in MFMA fragment order, one
+ * launch per 16 layers, tmdnet_cfconv_fused_image_bytes(filters, num_rbf) bytes per layer (a multiple of 16;
+ * 0 outside the envelope); layer l's image starts at img + l * that.  The image is a pure function of the
+ * weights: rebuild it whenever they may have changed.
+ * Envelope: float32, filters a multiple of 16 in [16, 128], 1 <= num_rbf <= 64, ADD / MEAN, SSP / SILU,
+ * h / grad_out rows 16-byte aligned with leading dimensions % 4 == 0 (0 = filters), img / out / gh 16-byte
+ * aligned; anything else returns TMDNET_UNSUPPORTED with nothing launched.  No atomics: bitwise reproducible. */
+size_t tmdnet_cfconv_fused_image_bytes(int filters, int num_rbf);
+int tmdnet_cfconv_fused_image(int n_layers, int filters, int num_rbf, const void* const* w1,
+                              const void* const* b1, const void* const* w2, const void* const* b2, void* img,
+                              void* stream);
+int tmdnet_cfconv_fused_fwd(int dtype, int aggr, int act, int rbf_type, int n_nodes, int filters, int num_rbf,
+                            const int32_t* row_ptr, const int32_t* src, int max_pairs, const void* h, int ld_h,
+                            const void* dist, const void* cutoff, const void* mu, const void* beta,
+                            double cutoff_lower, double cutoff_upper, const void* img, void* out, void* stream);
+/* Backward for grad_out g [N][filters] (ld_grad_out, 0 = filters), with w'_e = d w_e / d r_e:
+ *   gcut[e]  = scale_t sum_f g[t][f] h[s][f] w_e[f],   gdist[e] = scale_t C_e sum_f g[t][f] h[s][f] w'_e[f]
+ * for every slot < max_pairs (padding slots beyond row_ptr[N] and edges with an out-of-range source: zero) and,
+ * gh non-NULL,
+ *   gh[t] = sum_{e in row t} scale_s g[s] * w_e * C_e
+ * PRECONDITION of gh: the list is pair symmetric -- every edge (s -> t) has its reverse (t -> s) in row s with
+ * the same dist and cutoff (the neighbour-list builders and tmdnet_edge_geom_fwd guarantee it) -- so the
+ * filter of the edge leaving t is the one of the row's own edge.  The weights and the basis parameters are
+ * constants of the operator (no gradient). */
+int tmdnet_cfconv_fused_bwd(int dtype, int aggr, int act, int rbf_type, int n_nodes, int filters, int num_rbf,
+                            const int32_t* row_ptr, const int32_t* src, int max_pairs, const void* h, int ld_h,
+                            const void* dist, const void* cutoff, const void* mu, const void* beta,
+                            double cutoff_lower, double cutoff_upper, const void* img, const void* grad_out,
+                            int ld_grad_out, void* gh, void* gcut, void* gdist, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * TensorNet edge kernels (reference models/tensornet.py:287-332).
  * Tensors are COMPACT and component-major, [9][N][H]: per channel the coefficients

@@ -85,6 +85,10 @@ SIGNATURES = {
     "tmdnet_cfconv_fwd": (I, [I, I, I, I, P, P, I, P, I, P, I, P, P, P, P]),
     "tmdnet_cfconv_bwd": (I, [I, I, I, I, P, P, P, I, P, I, P, I, P, P, P, I, P, P, P, P]),
     "tmdnet_cfconv_bwd2": (I, [I, I, I, I, P, P, P, I, P, I, P, I, P, P, P, I, P, P, P, P, P, P, P, P]),
+    "tmdnet_cfconv_fused_image_bytes": (SZ, [I, I]),
+    "tmdnet_cfconv_fused_image": (I, [I, I, I, P, P, P, P, P, P]),
+    "tmdnet_cfconv_fused_fwd": (I, [I, I, I, I, I, I, I, P, P, I, P, I, P, P, P, P, D, D, P, P, P]),
+    "tmdnet_cfconv_fused_bwd": (I, [I, I, I, I, I, I, I, P, P, I, P, I, P, P, P, P, D, D, P, P, I, P, P, P, P]),
     "tmdnet_tn_embed_fwd": (I, [I, I, I, P, P, I, D, P, I, P, P, P, I, P, P, P, P]),
     "tmdnet_tn_embed_bwd": (I, [I, I, I, P, P, I, D, P, I, P, P, P, I, P, P, P, P, P, P, P, P, P]),
     "tmdnet_tn_embed_bwd2": (I, [I, I, I, P, P, I, D, P, I, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P,

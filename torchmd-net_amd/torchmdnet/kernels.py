@@ -1529,6 +1529,151 @@ def cfconv(h, w, C, graph, aggr="add", return_arg=False):
     return (out, arg) if return_arg else out
 
 
+# ----------------------------------------------------------------------------- fused filter convolution
+CFCONV_FUSED_INFERENCE_ONLY = ("torchmd-net_amd: optimized models are inference-only: the fused filter convolution "
+                               "(optimize()) has no second derivative, so a force loss or a Hessian cannot be "
+                               "differentiated through it; train the unoptimized model")
+
+
+def cfconv_fused_limits(filters, num_rbf, activation=None, aggr=None, dtype=None):
+    """None inside the envelope of ``tmdnet_cfconv_fused_*``, else a sentence naming the limit that is exceeded
+    (``optimize`` raises it as a ValueError; no GPU needed)."""
+    if dtype is not None and dtype != torch.float32:
+        return f"float32 only (got {dtype})"
+    if filters % 16 or not 16 <= filters <= 128:
+        return f"num_filters must be a multiple of 16 in [16, 128] (got {filters})"
+    if not 1 <= num_rbf <= 64:
+        return f"num_rbf must be in [1, 64] (got {num_rbf})"
+    if aggr is not None and aggr not in ("add", "mean"):
+        return f'aggr must be "add" or "mean" (got {aggr!r})'
+    if activation is not None and activation not in ("ssp", "silu", 0, 1):
+        return f'activation must be "ssp" or "silu" (got {activation!r})'
+    return None
+
+
+def cfconv_fused_image(mlps):
+    """The weight image of ``tmdnet_cfconv_fused_*`` for the filter networks ``mlps`` (each a
+    ``Sequential(Linear(R, F), act, Linear(F, F))``), all layers in one launch, built from the parameters as
+    they are NOW: returns (img uint8 [layers, bytes], F, R).  Never cached: call it once per evaluation."""
+    lib = nat.load()
+    w1 = [m[0].weight.detach() for m in mlps]
+    F_, R = w1[0].shape
+    nat.require_gpu(w1[0], "cfconv_fused")
+    tensors = []
+    cols = []
+    for get in (lambda m: m[0].weight, lambda m: m[0].bias, lambda m: m[2].weight, lambda m: m[2].bias):
+        col = []
+        for m in mlps:
+            t = get(m)
+            if t is not None:
+                if t.dtype != torch.float32:
+                    raise RuntimeError(f"torchmd-net_amd: cfconv_fused: unsupported floating type {t.dtype} (float32)")
+                t = t.detach().contiguous()
+                tensors.append(t)  # keeps a contiguous copy alive until the launch is queued
+            col.append(None if t is None else t.data_ptr())
+        cols.append((ctypes.c_void_p * len(mlps))(*col))
+    per = int(lib.tmdnet_cfconv_fused_image_bytes(int(F_), int(R)))
+    if per == 0:
+        raise RuntimeError("torchmd-net_amd: cfconv_fused: " + str(cfconv_fused_limits(int(F_), int(R))))
+    img = torch.empty((len(mlps), per), dtype=torch.uint8, device=w1[0].device)
+    rc = lib.tmdnet_cfconv_fused_image(len(mlps), int(F_), int(R), cols[0], cols[1], cols[2], cols[3], nat.ptr(img),
+                                       nat.stream(img.device))
+    nat.check(rc, "tmdnet_cfconv_fused_image")
+    return img, int(F_), int(R)
+
+
+def _cff_rows(t, width):
+    """Rows the fused kernels read as float4: unit element stride, 16-byte aligned rows."""
+    if t.stride(-1) != 1 or t.stride(0) < width or t.stride(0) % 4 or t.data_ptr() % 16:
+        t = t.contiguous()
+    return t
+
+
+def _cff_args(h, dist, C, graph, img, R, mu, beta, cl, cu, rbf_type, act, aggr):
+    N, nf = h.shape
+    return (nat.F32, nat.AGGR_CODES[aggr], int(act), int(rbf_type), N, nf, int(R), nat.ptr(graph.row_ptr),
+            nat.ptr(graph.src), graph.n_edges, nat.ptr(h), _ld(h), nat.ptr(dist), nat.ptr(C), nat.ptr(mu),
+            nat.ptr(beta), float(cl), float(cu), nat.ptr(img))
+
+
+class _CFConvFused(Function):
+    """out = cfconv_fused(h, dist, C): differentiable in h, dist and C; the weight image and the basis
+    parameters are constants."""
+
+    @staticmethod
+    def forward(ctx, h, dist, C, graph, img, R, mu, beta, cl, cu, rbf_type, act, aggr):
+        lib = nat.load()
+        out = torch.empty((h.shape[0], h.shape[1]), dtype=h.dtype, device=h.device)
+        rc = lib.tmdnet_cfconv_fused_fwd(*_cff_args(h, dist, C, graph, img, R, mu, beta, cl, cu, rbf_type, act, aggr),
+                                         nat.ptr(out), nat.stream(h.device))
+        nat.check(rc, "tmdnet_cfconv_fused_fwd")
+        ctx.graph, ctx.consts = graph, (R, cl, cu, rbf_type, act, aggr)
+        ctx.save_for_backward(h, dist, C, img, mu, beta)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        h, dist, C, img, mu, beta = ctx.saved_tensors
+        want_h = bool(ctx.needs_input_grad[0]) and _will_run(ctx.next_functions[0][0])
+        gh, gdist, gC = _CFConvFusedBwd.apply(_cff_rows(gout, h.shape[1]), h, dist, C, ctx.graph, img, mu, beta,
+                                              ctx.consts, want_h)
+        return (gh, gdist, gC) + (None,) * 10
+
+
+class _CFConvFusedBwd(Function):
+    """The first backward as a node of its own, so that differentiating it again fails loudly (as
+    ``once_differentiable`` would, with the package's message)."""
+
+    @staticmethod
+    def forward(ctx, gout, h, dist, C, graph, img, mu, beta, consts, want_h):
+        lib = nat.load()
+        R, cl, cu, rbf_type, act, aggr = consts
+        E = graph.n_edges
+        gh = torch.empty_like(h, memory_format=torch.contiguous_format) if want_h else None
+        ge = torch.empty((2, E), dtype=h.dtype, device=h.device)  # every slot written (padding zero)
+        rc = lib.tmdnet_cfconv_fused_bwd(*_cff_args(h, dist, C, graph, img, R, mu, beta, cl, cu, rbf_type, act, aggr),
+                                         nat.ptr(gout), gout.stride(0), nat.ptr(gh), nat.ptr(ge[0]), nat.ptr(ge[1]),
+                                         nat.stream(h.device))
+        nat.check(rc, "tmdnet_cfconv_fused_bwd")
+        return gh, ge[1], ge[0]
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise RuntimeError(CFCONV_FUSED_INFERENCE_ONLY)
+
+
+def cfconv_fused(h, distances, C, graph, w1, b1, w2, b2, rbf_params, cutoff_lower, cutoff_upper, rbf_type, act,
+                 aggr="add", image=None):
+    """Continuous-filter convolution with the filter network inside the edge kernel
+    (``tmdnet_cfconv_fused_*``): ``out[t] = scale_t sum_{e in row t} h[src_e] * w_e * C[e]`` with
+    ``w_e = W2 act(W1 rbf(distances[e]) + b1) + b2`` formed per edge in registers.  ``rbf_params`` = the basis
+    module's ``kernel_params()``; ``act`` = the activation code (``act_code``: SiLU 0, ShiftedSoftplus 1);
+    ``aggr`` add / mean.  ``image`` = one layer's slice of ``cfconv_fused_image`` (the model builds all layers
+    in one launch per evaluation); None: built here from ``w1, b1, w2, b2``.
+    Gradients flow to ``h``, ``distances`` and ``C`` only -- the weights and basis parameters are constants
+    of the op -- and only once: a double backward raises (optimized models are inference-only).  The ``h``
+    gradient relies on a pair-symmetric list (``distances`` and ``C`` equal on an edge and its reverse).
+    GPU float32 only; no CPU path."""
+    nat.require_gpu(h, "cfconv_fused")
+    if h.dtype != torch.float32:
+        raise RuntimeError(f"torchmd-net_amd: cfconv_fused: unsupported floating type {h.dtype} (float32)")
+    if aggr not in ("add", "mean"):
+        raise ValueError(f'cfconv_fused: aggr must be "add" or "mean" (got {aggr!r})')
+    nf, R = w1.shape
+    why = cfconv_fused_limits(int(nf), int(R), int(act))
+    if why is not None:
+        raise ValueError("cfconv_fused: " + why)
+    if image is None:
+        image = cfconv_fused_image([[_Lin(w1, b1), None, _Lin(w2, b2)]])[0][0]
+    mu, beta = rbf_params
+    return _CFConvFused.apply(_cff_rows(h, nf), distances.contiguous(), C.contiguous(), graph, image, int(R),
+                              mu.detach().contiguous(), beta.detach().contiguous(), float(cutoff_lower),
+                              float(cutoff_upper), int(rbf_type), int(act), aggr)
+
+
+_Lin = namedtuple("_Lin", ["weight", "bias"])
+
+
 # ----------------------------------------------------------------------------- activation
 def silu_launch(x, scale, out):
     lib = nat.load()
