@@ -120,6 +120,28 @@ int tmdnet_nl_backward_multi(int dtype, int n_atoms, const int32_t* row_ptr, con
                              const void* grad_distances2, const void* deltas, const void* distances,
                              void* grad_pos, void* stream);
 
+/* tmdnet_nl_backward_multi plus the per-molecule virial of the same pass.  The energy depends on the
+ * positions (and the box) only through the per-edge deltas; under a homogeneous strain pos -> pos (I + eps)^T,
+ * box -> box (I + eps)^T every delta scales the same way, so with g_e = dE/d delta_e (the g[e] above)
+ *   dE/d eps_ab = sum_e g_e[a] * delta_e[b]   over all directed edges (each direction is its own function
+ *   of pos: nothing is counted twice), and for molecule m, over the edges whose destination is in m,
+ *   virial[m][a][b] = - sum_e g_e[a] * delta_e[b] = - dE_m / d eps_ab        (stress = -virial / det(box)).
+ * The entry point sums the cotangents it is given: out[m][3a+b] = sum_e g[e][a] * delta[e][b].  A force pass
+ * seeds them with -1 (they are those of -E), so out is the virial itself; cotangents of +E give dE/d eps.
+ * Without a box it equals sum_{i in m} F_i[a] pos_i[b].  Slots with r == 0 (self loops, padding) add nothing.
+ * Row pass: k_nl_backward with nine more sums per lane -> atom_scratch [n_atoms][9] (per destination atom;
+ * scratch, not an output); grad_pos is bitwise tmdnet_nl_backward_multi's.  Sum pass: atom_scratch summed
+ * per molecule of batch (int64 [n_atoms]; values outside [0, n_mol) are skipped) into virial [n_mol][9]
+ * (overwritten), accumulated in double for either dtype, LDS bins, no global atomics.  Two launches, no host
+ * synchronisation.  n_mol outside tmdnet_atom_sum_fwd's envelope (1..8192): TMDNET_UNSUPPORTED, nothing
+ * launched.  virial NULL (batch / n_mol then unused): the row pass alone, one launch, for a caller that sums
+ * atom_scratch itself -- what the Python side does past that envelope. */
+int tmdnet_nl_backward_virial(int dtype, int n_atoms, const int32_t* row_ptr, const int32_t* transpose_map,
+                              int max_pairs, const void* grad_deltas, const void* grad_distances,
+                              const void* grad_distances2, const void* deltas, const void* distances,
+                              void* grad_pos, const int64_t* batch, int n_mol, void* virial,
+                              void* atom_scratch, void* stream);
+
 /* The same backward for ANY list the op returns (half lists with include_transpose=0, capacity-
  * truncated lists, padding slots -1): one lane per slot of neighbors [2][max_pairs], g scattered to
  * both ends with atomics, exactly the reference's index_add_ pair (neighbors_cuda.cu:58-68; so,

@@ -26,6 +26,10 @@ enum Status : int {
   kWorkspaceTooSmall = 4,
 };
 
+// Molecule ceiling of the per-molecule sums that keep one LDS bin per molecule (reduce.hip, the virial
+// sum of neighbors.hip): 8192 doubles are the 64 KiB a workgroup may declare.
+constexpr int kMaxMolecules = 8192;
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (TMD_WAVE - 1); }
 
 // XCD-contiguous block remap (bijective, cdna_hip_programming.md §5 "XCD swizzle"): hardware deals

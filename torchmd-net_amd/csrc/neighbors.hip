@@ -477,6 +477,84 @@ __global__ void k_nl_backward(int n, const int* __restrict__ row_ptr, const int3
   }
 }
 
+// k_nl_backward plus the strain derivative of the same pass (tmdnet_nl_backward_virial): per row t,
+// w[t][a][b] = sum_{k in row t} g[k][a] * delta[k][b] beside gpos[t].  The gpos arithmetic is
+// k_nl_backward's statement for statement (same edge order, same reduction), so it comes out bitwise
+// equal; the nine extra sums only read values the row pass holds already (g[k], delta[k]).
+template <typename T>
+__global__ void k_nl_backward_virial(int n, const int* __restrict__ row_ptr, const int32_t* __restrict__ tr,
+                                     int cap, const T* __restrict__ gd, const T* __restrict__ gr,
+                                     const T* __restrict__ gr2, const T* __restrict__ dl,
+                                     const T* __restrict__ r, T* __restrict__ gpos, T* __restrict__ atom9) {
+  const int gt = blockIdx.x * blockDim.x + threadIdx.x;
+  const int t = gt / kNlLanes, lane = gt % kNlLanes;
+  V3<T> acc{T(0), T(0), T(0)};
+  T w[9];
+#pragma unroll
+  for (int c = 0; c < 9; ++c) w[c] = T(0);
+  if (t < n) {
+    const int b = min(row_ptr[t], cap), e = min(row_ptr[t + 1], cap);
+    for (int k = b + lane; k < e; k += kNlLanes) {
+      const V3<T> gm = edge_grad(k, gd, gr, gr2, dl, r);
+      acc.x -= gm.x; acc.y -= gm.y; acc.z -= gm.z;
+      const T dx = dl[3 * k + 0], dy = dl[3 * k + 1], dz = dl[3 * k + 2];
+      w[0] += gm.x * dx; w[1] += gm.x * dy; w[2] += gm.x * dz;
+      w[3] += gm.y * dx; w[4] += gm.y * dy; w[5] += gm.y * dz;
+      w[6] += gm.z * dx; w[7] += gm.z * dy; w[8] += gm.z * dz;
+      const int k2 = tr[k];
+      if (k2 >= 0) {
+        const V3<T> gp = edge_grad(k2, gd, gr, gr2, dl, r);
+        acc.x += gp.x; acc.y += gp.y; acc.z += gp.z;
+      }
+    }
+  }
+  acc.x = group_sum16(acc.x);
+  acc.y = group_sum16(acc.y);
+  acc.z = group_sum16(acc.z);
+#pragma unroll
+  for (int c = 0; c < 9; ++c) w[c] = group_sum16(w[c]);
+  if (t < n && lane == 0) {
+    gpos[3 * t + 0] = acc.x;
+    gpos[3 * t + 1] = acc.y;
+    gpos[3 * t + 2] = acc.z;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) atom9[(size_t)9 * t + c] = w[c];
+  }
+}
+
+// Per-molecule sum of the row pass's [n][9] values: block c sums component c of every atom into LDS
+// bins (n_mol <= kMaxMolecules, as the energy reduction of reduce.hip), in DOUBLE whatever T: up to
+// 50k atoms x mixed signs per bin, fp32 accumulation would lose what the row pass kept.  Thread t walks
+// a contiguous chunk and flushes its running sum when the molecule changes (k_atom_runs' scheme: any
+// batch order is summed correctly, molecule-contiguous ones cost ~1 LDS atomic per thread).  No global
+// atomics; batch values outside [0, n_mol) are skipped.
+template <typename T>
+__global__ __launch_bounds__(1024) void k_virial_mol_sum(int n, int n_mol, const T* __restrict__ atom9,
+                                                         const int64_t* __restrict__ batch,
+                                                         T* __restrict__ virial) {
+  __shared__ double bins[kMaxMolecules];
+  const int c = blockIdx.x;  // 0..8
+  for (int b = threadIdx.x; b < n_mol; b += blockDim.x) bins[b] = 0.0;
+  __syncthreads();
+  const int chunk = (n + (int)blockDim.x - 1) / (int)blockDim.x;
+  const int i0 = (int)min((long long)n, (long long)threadIdx.x * chunk);
+  const int i1 = (int)min((long long)n, (long long)i0 + chunk);
+  int64_t cur = -1;
+  double acc = 0.0;
+  for (int i = i0; i < i1; ++i) {
+    const int64_t b = batch[i];
+    if (b != cur) {
+      if (cur >= 0 && cur < n_mol) atomicAdd(&bins[cur], acc);
+      cur = b;
+      acc = 0.0;
+    }
+    acc += (double)atom9[(size_t)9 * i + c];
+  }
+  if (cur >= 0 && cur < n_mol) atomicAdd(&bins[cur], acc);
+  __syncthreads();
+  for (int b = threadIdx.x; b < n_mol; b += blockDim.x) virial[(size_t)9 * b + c] = (T)bins[b];
+}
+
 // Second order of k_nl_backward (the double backward of NeighborAutograd's index_add pair,
 // reference neighbors_cuda.cu:25-89, which the reference differentiates through autograd).  With
 // gg = cotangent of gpos and, per edge e = (s -> t), w = gg[s] - gg[t], u = dl/r:
@@ -781,6 +859,45 @@ extern "C" int tmdnet_nl_backward_multi(int dtype, int n_atoms, const int32_t* r
   else
     return kUnsupported;
   return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
+}
+
+template <typename T>
+static int nl_backward_virial(int n_atoms, const int32_t* row_ptr, const int32_t* transpose_map, int max_pairs,
+                              const void* grad_deltas, const void* grad_distances, const void* grad_distances2,
+                              const void* deltas, const void* distances, void* grad_pos, const int64_t* batch,
+                              int n_mol, void* virial, void* atom_scratch, hipStream_t st) {
+  const int tb = 256;
+  dim3 g((unsigned)(((size_t)n_atoms * nl::kNlLanes + tb - 1) / tb));
+  hipLaunchKernelGGL(nl::k_nl_backward_virial<T>, g, dim3(tb), 0, st, n_atoms, row_ptr, transpose_map, max_pairs,
+                     (const T*)grad_deltas, (const T*)grad_distances, (const T*)grad_distances2,
+                     (const T*)deltas, (const T*)distances, (T*)grad_pos, (T*)atom_scratch);
+  if (hipGetLastError() != hipSuccess) return kLaunchFailed;
+  if (!virial) return kOk;  // the row pass alone: the caller sums atom_scratch
+  hipLaunchKernelGGL(nl::k_virial_mol_sum<T>, dim3(9), dim3(1024), 0, st, n_atoms, n_mol,
+                     (const T*)atom_scratch, batch, (T*)virial);
+  return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
+}
+
+extern "C" int tmdnet_nl_backward_virial(int dtype, int n_atoms, const int32_t* row_ptr,
+                                         const int32_t* transpose_map, int max_pairs, const void* grad_deltas,
+                                         const void* grad_distances, const void* grad_distances2,
+                                         const void* deltas, const void* distances, void* grad_pos,
+                                         const int64_t* batch, int n_mol, void* virial, void* atom_scratch,
+                                         void* stream) {
+  if (n_atoms <= 0 || !row_ptr || !grad_pos || !atom_scratch || (virial && !batch)) return kBadArgument;
+  // the molecule envelope of tmdnet_atom_sum_fwd (one LDS bin per molecule); nothing is launched outside
+  // it -- the caller asks for the row pass alone (virial NULL) and sums the per-atom values itself
+  if (virial && (n_mol <= 0 || n_mol > kMaxMolecules)) return kUnsupported;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == TMDNET_F32)
+    return nl_backward_virial<float>(n_atoms, row_ptr, transpose_map, max_pairs, grad_deltas, grad_distances,
+                                     grad_distances2, deltas, distances, grad_pos, batch, n_mol, virial,
+                                     atom_scratch, st);
+  if (dtype == TMDNET_F64)
+    return nl_backward_virial<double>(n_atoms, row_ptr, transpose_map, max_pairs, grad_deltas, grad_distances,
+                                      grad_distances2, deltas, distances, grad_pos, batch, n_mol, virial,
+                                      atom_scratch, st);
+  return kUnsupported;
 }
 
 extern "C" int tmdnet_nl_backward(int dtype, int n_atoms, const int32_t* row_ptr,

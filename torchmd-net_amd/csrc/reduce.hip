@@ -10,7 +10,7 @@
 namespace tmd {
 namespace red {
 
-constexpr int kMaxBins = 8192;
+constexpr int kMaxBins = kMaxMolecules;
 
 template <typename T>
 __global__ __launch_bounds__(1024) void k_atom_sum(int n, int n_mol, const T* __restrict__ x,

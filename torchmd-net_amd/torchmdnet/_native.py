@@ -26,6 +26,8 @@ BWD2_ACC_EDGE, BWD2_ACC_GVEC = 8, 16
 ET_TWO_PASS = 64
 ET_PREACT = 128  # pk / pv (dpk / dpv) hold the activated rows S (D) of tmdnet_proj_act_f32
 
+UNSUPPORTED = 2  # TMDNET_UNSUPPORTED: outside an entry point's envelope, nothing launched
+
 _STATUS = {1: "bad argument", 2: "unsupported configuration", 3: "kernel launch failed",
            4: "workspace too small"}
 
@@ -43,6 +45,7 @@ SIGNATURES = {
                                         P]),
     "tmdnet_nl_backward": (I, [I, I, P, P, I, P, P, P, P, P, P]),
     "tmdnet_nl_backward_multi": (I, [I, I, P, P, I, P, P, P, P, P, P, P]),
+    "tmdnet_nl_backward_virial": (I, [I, I, P, P, I, P, P, P, P, P, P, P, I, P, P, P]),
     "tmdnet_nl_backward2": (I, [I, I, P, P, P, I, P, P, P, P, P, P, P, P]),
     "tmdnet_nl_backward_edges": (I, [I, I, P, I, P, P, P, P, P, P]),
     "tmdnet_edge_geom_fwd": (I, [I, I, I, I, P, P, P, P, P, P, D, D, P, P, P, P]),

@@ -11,6 +11,8 @@ whole forward + autograd force pass: ~600 launches become one graph launch.
     y, neg_dy = gm(pos_new)                              # copy-in + replay (same z/batch layout)
     gm.check_capacity()                                  # raises if a replay overflowed capacity
 
+``GraphedEnergyForces(..., virial=True)`` also keeps the per-molecule virial of every replay in ``gm.virial``.
+
 Pair priors (ZBL, D2, Coulomb) build a neighbour list of their own: each gets its own static capacity from its
 own warm-up pair count (``prior_capacity`` overrides it for all of them) and its own overflow flag, which
 ``check_capacity`` reads besides the representation model's.
@@ -38,7 +40,8 @@ def refuse_pair_priors(model):
 
 
 class GraphedEnergyForces:
-    def __init__(self, model, z, pos, batch, edge_capacity=None, margin=1.25, warmup=3, prior_capacity=None):
+    def __init__(self, model, z, pos, batch, edge_capacity=None, margin=1.25, warmup=3, prior_capacity=None,
+                 virial=False):
         if not model.derivative:
             raise ValueError("GraphedEnergyForces captures TorchMD_Net(derivative=True)")
         rep = model.representation_model
@@ -75,13 +78,19 @@ class GraphedEnergyForces:
         s = torch.cuda.Stream(device=dev)
         s.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(s):
-            for _ in range(warmup):
-                model(self.z, self.pos, self.batch)
+            for _ in range(warmup):  # the captured call itself, so every kernel it launches has run once
+                (model.energy_forces_virial if virial else model)(self.z, self.pos, self.batch)
         torch.cuda.current_stream(dev).wait_stream(s)
         torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
+        # virial=True: the capture goes through energy_forces_virial; ``self.virial`` is the static
+        # [n_mol, 3, 3] tensor (-dE_m/d eps) every replay refreshes, n_mol the warm-up's frozen molecule count
+        self.virial = None
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            self.y, self.neg_dy = model(self.z, self.pos, self.batch)
+            if virial:
+                self.y, self.neg_dy, self.virial = model.energy_forces_virial(self.z, self.pos, self.batch)
+            else:
+                self.y, self.neg_dy = model(self.z, self.pos, self.batch)
         torch.cuda.synchronize(dev)
         # device flag written by every replay (lives in the graph's memory pool)
         self.overflow = rep.distance.last_overflow

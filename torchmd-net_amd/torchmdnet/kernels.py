@@ -249,20 +249,129 @@ class _NeighborGeom(Function):
         return gpos, None, None, None
 
 
+class VirialSink:
+    """Where one energy + force evaluation collects its per-molecule virial (``out`` [n_mol, 3, 3] =
+    -dE_m/d eps, include/tmdnet.h ``tmdnet_nl_backward_virial``).  One shot: ``build_graph`` attaches the
+    open sink to every EdgeGraph it returns (the representation model's and each pair prior's), the force
+    pass of each such graph adds its share, and ``close`` -- when the public call returns -- ends it: a
+    later backward over the same graph (a retained graph, a force-matching loss) finds it closed and leaves
+    ``out`` alone.  The sink rides on the graph object, not on a thread-local: autograd runs the force pass
+    of GPU tensors on its device thread, not on the caller's."""
+    __slots__ = ("n_mol", "batch", "out", "open", "attached")
+
+    def __init__(self, n_mol, batch, out):
+        self.n_mol, self.batch, self.out = int(n_mol), batch, out
+        self.open = True
+        self.attached = 0
+
+    def close(self):
+        self.open = False
+        self.batch = self.out = None  # the graphs that still hold the sink keep no tensor alive through it
+
+
+_VIRIAL_SINK = None  # the open sink of the evaluation being recorded (read by build_graph only)
+
+
+class virial_sink:
+    """``with virial_sink(n_mol, batch, dtype) as sink:`` -- graphs built inside add their force pass's
+    virial into ``sink.out`` (zeros [n_mol, 3, 3], allocated here; keep a reference before the block ends)."""
+
+    def __init__(self, n_mol, batch, dtype):
+        out = torch.zeros((int(n_mol), 3, 3), dtype=dtype, device=batch.device)
+        self.sink = VirialSink(n_mol, batch.contiguous(), out)
+
+    def __enter__(self):
+        global _VIRIAL_SINK
+        if _VIRIAL_SINK is not None:
+            raise RuntimeError("a virial sink is already open (energy_forces_virial does not nest)")
+        _VIRIAL_SINK = self.sink
+        return self.sink
+
+    def __exit__(self, *exc):
+        global _VIRIAL_SINK
+        _VIRIAL_SINK = None
+        self.sink.close()
+        return False
+
+
+def _attach_virial_sink(graph):
+    sink = _VIRIAL_SINK
+    if sink is not None and sink.open:
+        graph.virial_sink = sink
+        sink.attached += 1
+
+
+def nl_backward_virial_composite(gd, gr, gr2, deltas, distances, dst, batch, n_mol):
+    """Plain-torch restatement of tmdnet_nl_backward_virial's second output (the CPU path, the fallback's
+    yardstick and the tests'): g_e = gd_e + delta_e / r_e * (gr_e + gr2_e), zero where r_e == 0, and
+    out[m] = sum over the edges e whose destination atom is in molecule m of g_e (x) delta_e -> [n_mol, 3, 3].
+    With the cotangents of a force pass (seeded with -1) that is the virial -dE_m/d eps."""
+    zero = distances == 0
+    g = torch.zeros_like(deltas) if gd is None else gd
+    gsum = _sum_opt([gr, gr2])
+    if gsum is not None:
+        r = torch.where(zero, torch.ones_like(distances), distances)
+        g = g + deltas * (gsum / r).unsqueeze(1)
+    g = torch.where(zero.unsqueeze(1), torch.zeros_like(g), g)
+    dl = torch.where(zero.unsqueeze(1), torch.zeros_like(deltas), deltas)  # a padding slot may hold anything
+    w = g.unsqueeze(2) * dl.unsqueeze(1)
+    mol = batch.index_select(0, dst.long().clamp(0, batch.shape[0] - 1))
+    return torch.zeros((int(n_mol), 3, 3), dtype=deltas.dtype, device=deltas.device).index_add_(0, mol, w)
+
+
+def nl_backward_virial(pos, gd, gr, gr2, deltas, distances, graph, batch, n_mol):
+    """(grad_pos, out [n_mol, 3, 3]) of tmdnet_nl_backward_virial: the neighbour op's position gradient
+    (bitwise tmdnet_nl_backward_multi's) and, from the same row pass, out[m] = sum_e g_e (x) delta_e over the
+    edges into molecule m.  Above the entry point's molecule ceiling the row pass runs alone and its
+    per-atom sums are added per molecule with index_add, in double as the kernel's own sum stage."""
+    lib = nat.load()
+    nat.require_gpu(pos, "nl_backward_virial")
+    n = pos.shape[0]
+    if batch.dtype != torch.int64 or batch.shape != (n,) or not batch.is_contiguous() or batch.device != pos.device:
+        raise RuntimeError('Expected "batch" to be a contiguous int64 vector matching "positions"')
+    if deltas.shape != (graph.n_edges, 3) or distances.shape != (graph.n_edges,):
+        raise RuntimeError("nl_backward_virial: deltas / distances do not match the graph's edge count")
+    deltas, distances = deltas.contiguous(), distances.contiguous()
+    gpos = torch.empty_like(pos)
+    scratch = torch.empty((n, 9), dtype=pos.dtype, device=pos.device)
+    out = torch.empty((int(n_mol), 9), dtype=pos.dtype, device=pos.device)
+
+    def launch(out_):
+        return lib.tmdnet_nl_backward_virial(nat.dtype_code(pos.dtype), n, nat.ptr(graph.row_ptr),
+                                             nat.ptr(graph.transpose), graph.n_edges, nat.ptr(gd), nat.ptr(gr),
+                                             nat.ptr(gr2), nat.ptr(deltas), nat.ptr(distances), nat.ptr(gpos),
+                                             nat.ptr(batch), int(n_mol), nat.ptr(out_), nat.ptr(scratch),
+                                             nat.stream(pos.device))
+
+    rc = launch(out)
+    if rc == nat.UNSUPPORTED and pos.dtype in (torch.float32, torch.float64) and int(n_mol) > 0:
+        nat.check(launch(None), "tmdnet_nl_backward_virial")  # no virial pointer: the row pass alone
+        out = torch.zeros((int(n_mol), 9), dtype=torch.float64, device=pos.device).index_add_(
+            0, batch, scratch.double()).to(pos.dtype)
+    else:
+        nat.check(rc, "tmdnet_nl_backward_virial")
+    return gpos, out.view(-1, 3, 3)
+
+
 class _NeighborGeomBwd(Function):
     @staticmethod
     def forward(ctx, pos, g_deltas, g_dist, deltas, distances, graph, g_dist2=None):
         lib = nat.load()
         n = pos.shape[0]
-        gpos = torch.empty_like(pos)
         gd = None if g_deltas is None else g_deltas.contiguous()
         gr = None if g_dist is None else g_dist.contiguous()
         gr2 = None if g_dist2 is None else g_dist2.contiguous()
-        rc = lib.tmdnet_nl_backward_multi(nat.dtype_code(pos.dtype), n, nat.ptr(graph.row_ptr),
-                                          nat.ptr(graph.transpose), graph.n_edges, nat.ptr(gd), nat.ptr(gr),
-                                          nat.ptr(gr2), nat.ptr(deltas), nat.ptr(distances), nat.ptr(gpos),
-                                          nat.stream(pos.device))
-        nat.check(rc, "tmdnet_nl_backward_multi")
+        sink = getattr(graph, "virial_sink", None)
+        if sink is not None and sink.open:  # the force pass of energy_forces_virial: same gpos, plus its virial
+            gpos, w = nl_backward_virial(pos, gd, gr, gr2, deltas, distances, graph, sink.batch, sink.n_mol)
+            sink.out.add_(w)
+        else:
+            gpos = torch.empty_like(pos)
+            rc = lib.tmdnet_nl_backward_multi(nat.dtype_code(pos.dtype), n, nat.ptr(graph.row_ptr),
+                                              nat.ptr(graph.transpose), graph.n_edges, nat.ptr(gd), nat.ptr(gr),
+                                              nat.ptr(gr2), nat.ptr(deltas), nat.ptr(distances), nat.ptr(gpos),
+                                              nat.stream(pos.device))
+            nat.check(rc, "tmdnet_nl_backward_multi")
         ctx.graph = graph
         ctx.two = gr2 is not None
         # the second order sees the summed distance gradient (both slots get its gradient); summed there,
@@ -405,6 +514,7 @@ def build_graph(pos, batch, cutoff_lower, cutoff_upper, max_num_pairs, loop=True
         if fused_pairs is not None:
             graph._pairs = fused_pairs
             graph.num_pair_rows_dev = nrows
+        _attach_virial_sink(graph)
         deltas, distances, distances2 = _NeighborGeom.apply(pos, graph, dl, dist)
         graph.deltas = deltas
         graph.distances = distances
@@ -423,6 +533,7 @@ def build_graph(pos, batch, cutoff_lower, cutoff_upper, max_num_pairs, loop=True
     graph.sorted_rows = strategy != "cell"  # brute / shared rows list sources ascending
     if fused_pairs is not None and graph.symmetric:  # the numbering of the kept prefix of rows
         graph._pairs = (fused_pairs[0][:E], fused_pairs[1][:(E + n) // 2])
+    _attach_virial_sink(graph)
     deltas, distances, distances2 = _NeighborGeom.apply(pos, graph, dl[:E], dist[:E])
     graph.deltas = deltas
     graph.distances = distances

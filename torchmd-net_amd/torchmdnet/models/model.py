@@ -307,6 +307,42 @@ class TorchMD_Net(nn.Module):
             return y, neg_dy
         return y, None
 
+    @torch.jit.unused
+    def energy_forces_virial(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None,
+                             q: Optional[Tensor] = None, s: Optional[Tensor] = None,
+                             extra_args: Optional[Dict[str, Tensor]] = None
+                             ) -> Tuple[Tensor, Optional[Tensor], Tensor]:
+        """``forward`` plus the per-molecule virial: returns (y, neg_dy, virial) with (y, neg_dy) exactly
+        ``forward``'s and ``virial[m][a][b] = -dE_m/d eps_ab`` ([n_mol, 3, 3]) for the homogeneous strain
+        pos -> pos (I + eps)^T, box -> box (I + eps)^T; without a box that is sum_{i in m} F_i[a] pos_i[b].
+        Stress = -virial / det(box).  The virial is summed inside the force pass's neighbour backward kernel
+        (tmdnet_nl_backward_virial) over the model's graph and each pair prior's; it is detached (no
+        gradient of the virial: stress labels cannot be trained on yet) and has the dtype of ``y``.  Eager
+        only: the scripted path and tmdnet::et_energy_forces produce no virial."""
+        from .. import kernels
+        from .utils import check_stream_capturing
+        from .wrappers import BaseWrapper
+        if not self.derivative:
+            raise ValueError("energy_forces_virial needs TorchMD_Net(derivative=True): the virial is summed "
+                             "in the force pass")
+        if isinstance(self.representation_model, BaseWrapper):
+            raise ValueError(f"energy_forces_virial does not support a wrapped representation model "
+                             f"({type(self.representation_model).__name__}): its atoms are not the caller's")
+        nat_batch = torch.zeros_like(z) if batch is None else batch
+        if pos.is_cuda and check_stream_capturing():
+            n_mol = int(self.output_model.dim_size)  # frozen by the warm-up call: no host read in a capture
+            if n_mol <= 0:
+                raise RuntimeError("Warming up is needed before capturing the model into a CUDA graph")
+        else:
+            n_mol = int(nat_batch.max()) + 1 if nat_batch.numel() else 0
+        cdtype = torch.float32 if self._half_storage else pos.dtype
+        with kernels.virial_sink(n_mol, nat_batch, cdtype) as sink:
+            virial = sink.out
+            y, neg_dy = self(z, pos, batch, q=q, s=s, extra_args=extra_args)
+            if sink.attached == 0:
+                raise RuntimeError("energy_forces_virial: no neighbour graph was built by this evaluation")
+        return y, neg_dy, virial.to(y.dtype)
+
     def _forward_script(self, z: Tensor, pos: Tensor, batch: Tensor, q: Optional[Tensor], s: Optional[Tensor],
                         extra_args: Optional[Dict[str, Tensor]]) -> Tuple[Tensor, Optional[Tensor]]:
         """TorchScript body: reference model.py:252-300 line for line (the representation model's
