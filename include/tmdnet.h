@@ -35,7 +35,7 @@ enum { TMDNET_ACC_GRADS = 32 };
  * Planar rows make every 16-byte-per-lane load of a row segment contiguous (measured 4-7 % on the C5
  * forward).  Gradients of v / pv are written in the same layout. */
 enum { TMDNET_ET_V_PLANAR = 4 };
-/* tmdnet_et_message_bwd2_ex flags: accumulate d_cut / d_unit (ACC_EDGE) and d_grad_vec (ACC_GVEC)
+/* tmdnet_et_message_bwd2 flags: accumulate d_cut / d_unit (ACC_EDGE) and d_grad_vec (ACC_GVEC)
  * into the caller's buffers instead of overwriting them. */
 enum { TMDNET_BWD2_ACC_EDGE = 8, TMDNET_BWD2_ACC_GVEC = 16 };
 /* tmdnet_et_message_bwd accumulate bit: the dr-mode backward as the two passes (destination, then
@@ -52,8 +52,8 @@ enum { TMDNET_ET_TWO_PASS = 64 };
  * (ACC_VEC_RESIDUAL, ACC_EDGE), 4, 32 (ACC_GRADS), 64 (TWO_PASS), 128, 0xff00; _bwd2 flags: 4, 8, 16
  * (BWD2_ACC_*), 0xff00. */
 enum { TMDNET_ET_PREACT = 128 };
-/* Activations of the ET message entry points (tmdnet_et_message_fwd flags, _bwd accumulate, _bwd2 /
- * _bwd2_ex flags): bits 8-11 = the dk / dv projections' activation (reference EquivariantMultiHeadAttention
+/* Activations of the ET message entry points (tmdnet_et_message_fwd flags, _bwd accumulate, _bwd2
+ * flags): bits 8-11 = the dk / dv projections' activation (reference EquivariantMultiHeadAttention
  * `activation`, torchmd_et.py:285-291), bits 12-15 = the attention activation (`attn_activation`,
  * torchmd_et.py:316), coded as the reference act_class_mapping (models/utils.py:579-584): SiLU (0, the
  * default), ShiftedSoftplus, Tanh, Sigmoid.  Other codes: TMDNET_BAD_ARGUMENT.  (The fused-projection
@@ -76,51 +76,37 @@ enum { TMDNET_ACT_SILU = 0, TMDNET_ACT_SSP = 1, TMDNET_ACT_TANH = 2, TMDNET_ACT_
  * box9: row-major 3x3 box vectors on the HOST (reduced triclinic form), may be NULL if not periodic.
  * The cell strategy needs a diagonal box (the caller supplies 3*cutoff when not periodic, as
  * reference utils.py:199-202 does).
+ * Pair numbering (optional): pair_row [max_pairs] and pair_edge [n_pair_slots > 0] given together are filled
+ * as tmdnet_pair_index fills them, with no extra launch (the canonical counts ride on the count pass, their
+ * scan on the row scan, the numbers on the transpose pass).  It needs sorted rows and the reversed edges:
+ * brute / shared strategy, include_transpose and a transpose_map -- else TMDNET_BAD_ARGUMENT (for the cell
+ * strategy, use tmdnet_pair_index).  num_pair_rows[0] (int32 on the device, nullable) then receives the
+ * number of pair rows: the canonical edges the kept list holds, at most n_pair_slots -- every pair_row of a
+ * kept edge is below it, so a consumer of the pair rows (tmdnet_proj_f32's rows) can stop there; written by
+ * the row scan, no host sync.  pair_row NULL: no numbering, and pair_edge, n_pair_slots, num_pair_rows must
+ * be NULL / 0 / NULL (TMDNET_BAD_ARGUMENT otherwise, nothing launched).
  */
 size_t tmdnet_nl_workspace_bytes(int n_atoms, int strategy, const double* box9, double cutoff_upper);
 int tmdnet_nl_build(int dtype, int strategy, const void* pos, const int64_t* batch, int n_atoms,
                     const double* box9, int use_periodic, double cutoff_lower, double cutoff_upper,
                     int max_pairs, int loop, int include_transpose, int32_t* neighbors, void* deltas,
                     void* distances, int32_t* num_pairs, int32_t* row_ptr, int32_t* transpose_map,
-                    int pad_output, void* workspace, size_t workspace_bytes, void* stream);
-/* tmdnet_nl_build plus the pair numbering of tmdnet_pair_index in the same launches (sorted rows:
- * brute / shared strategies, include_transpose with a transpose_map): pair_row [max_pairs] and
- * pair_edge [n_pair_slots] as tmdnet_pair_index fills them, with no extra launch (the canonical
- * counts ride on the count pass, their scan on the row scan, the numbers on the transpose pass).
- * The cell strategy returns TMDNET_BAD_ARGUMENT here (use tmdnet_pair_index). */
-int tmdnet_nl_build_paired(int dtype, int strategy, const void* pos, const int64_t* batch, int n_atoms,
-                           const double* box9, int use_periodic, double cutoff_lower, double cutoff_upper,
-                           int max_pairs, int loop, int include_transpose, int32_t* neighbors, void* deltas,
-                           void* distances, int32_t* num_pairs, int32_t* row_ptr, int32_t* transpose_map,
-                           int pad_output, void* workspace, size_t workspace_bytes, int32_t* pair_row,
-                           int32_t* pair_edge, int n_pair_slots, void* stream);
-/* tmdnet_nl_build_paired that also leaves the number of pair rows on the device: num_pair_rows[0] (int32,
- * nullable) = the number of canonical edges the kept list holds, at most n_pair_slots -- every pair_row
- * of a kept edge is below it, so a consumer of the pair rows (tmdnet_proj_rows_f32) can stop there.
- * Written by the row scan: no extra launch, no host sync. */
-int tmdnet_nl_build_paired_rows(int dtype, int strategy, const void* pos, const int64_t* batch, int n_atoms,
-                                const double* box9, int use_periodic, double cutoff_lower, double cutoff_upper,
-                                int max_pairs, int loop, int include_transpose, int32_t* neighbors, void* deltas,
-                                void* distances, int32_t* num_pairs, int32_t* row_ptr, int32_t* transpose_map,
-                                int pad_output, void* workspace, size_t workspace_bytes, int32_t* pair_row,
-                                int32_t* pair_edge, int n_pair_slots, int32_t* num_pair_rows, void* stream);
+                    int pad_output, void* workspace, size_t workspace_bytes, int32_t* pair_row,
+                    int32_t* pair_edge, int n_pair_slots, int32_t* num_pair_rows, void* stream);
 
 /* Backward of the neighbour op w.r.t. positions (reference NeighborAutograd::backward,
  * neighbors_cuda.cu:43-71) as a segmented CSR reduction (no atomics, deterministic):
  *   g[e] = r[e]==0 ? 0 : gdelta[e] + delta[e]/r[e]*gr[e];  dpos[n] = sum_{e in row n} g[T[e]] - g[e].
- * Requires a symmetric list (include_transpose=1) and its transpose_map.  grad_deltas or
- * grad_distances may be NULL (treated as zero).  grad_pos [n_atoms][3] is overwritten. */
+ * Requires a symmetric list (include_transpose=1) and its transpose_map.  grad_deltas, grad_distances and
+ * grad_distances2 may each be NULL (treated as zero); gr = grad_distances + grad_distances2, the second
+ * being the distances' second consumer (the ET layer stack's force-pass g_r beside the edge geometry's), so
+ * no separate add launch forms the sum.  grad_pos [n_atoms][3] is overwritten. */
 int tmdnet_nl_backward(int dtype, int n_atoms, const int32_t* row_ptr, const int32_t* transpose_map,
                        int max_pairs, const void* grad_deltas, const void* grad_distances,
-                       const void* deltas, const void* distances, void* grad_pos, void* stream);
-/* The same with a second distance gradient (NULL allowed) summed in: the distances' second consumer
- * (the ET layer stack's force-pass g_r beside the edge geometry's), no separate add launch. */
-int tmdnet_nl_backward_multi(int dtype, int n_atoms, const int32_t* row_ptr, const int32_t* transpose_map,
-                             int max_pairs, const void* grad_deltas, const void* grad_distances,
-                             const void* grad_distances2, const void* deltas, const void* distances,
-                             void* grad_pos, void* stream);
+                       const void* grad_distances2, const void* deltas, const void* distances,
+                       void* grad_pos, void* stream);
 
-/* tmdnet_nl_backward_multi plus the per-molecule virial of the same pass.  The energy depends on the
+/* tmdnet_nl_backward plus the per-molecule virial of the same pass.  The energy depends on the
  * positions (and the box) only through the per-edge deltas; under a homogeneous strain pos -> pos (I + eps)^T,
  * box -> box (I + eps)^T every delta scales the same way, so with g_e = dE/d delta_e (the g[e] above)
  *   dE/d eps_ab = sum_e g_e[a] * delta_e[b]   over all directed edges (each direction is its own function
@@ -130,7 +116,7 @@ int tmdnet_nl_backward_multi(int dtype, int n_atoms, const int32_t* row_ptr, con
  * seeds them with -1 (they are those of -E), so out is the virial itself; cotangents of +E give dE/d eps.
  * Without a box it equals sum_{i in m} F_i[a] pos_i[b].  Slots with r == 0 (self loops, padding) add nothing.
  * Row pass: k_nl_backward with nine more sums per lane -> atom_scratch [n_atoms][9] (per destination atom;
- * scratch, not an output); grad_pos is bitwise tmdnet_nl_backward_multi's.  Sum pass: atom_scratch summed
+ * scratch, not an output); grad_pos is bitwise tmdnet_nl_backward's.  Sum pass: atom_scratch summed
  * per molecule of batch (int64 [n_atoms]; values outside [0, n_mol) are skipped) into virial [n_mol][9]
  * (overwritten), accumulated in double for either dtype, LDS bins, no global atomics.  Two launches, no host
  * synchronisation.  n_mol outside tmdnet_atom_sum_fwd's envelope (1..8192): TMDNET_UNSUPPORTED, nothing
@@ -172,27 +158,18 @@ int tmdnet_nl_backward2(int dtype, int n_atoms, const int32_t* row_ptr, const in
  * rbf_type EXPNORM: f[e][k] = C0(r) exp(-beta_k (exp(alpha (cl - r)) - mu_k)^2), C0 = cosine
  *   cutoff (0, cu), alpha = 5/(cu-cl);  GAUSS: f[e][k] = exp(coeff * (r - mu_k)^2) (coeff = beta_0).
  * C[e] = CosineCutoff(cl, cu)(r);  unit[e] = self edge (src==dst) ? delta : delta / |delta|.
- * Any output pointer may be NULL (not computed). */
+ * Any output pointer may be NULL (not computed).
+ * rows (int32 [n_rows], nullable): the RBF features of the edges rows[p] also go into rbf_rows
+ * [n_rows][num_rbf] in the same launch (the ET layer stack's pair rows: replaces a gather of rbf; required
+ * when n_rows > 0), and with drbf_rows (nullable) d rbf / d r of the same rows into drbf_rows
+ * [n_rows][num_rbf] (the ET force pass's dr-mode operand; replaces a tmdnet_rbf_deriv launch).  rows NULL:
+ * no row outputs, and n_rows, rbf_rows, drbf_rows must be 0 / NULL / NULL.  n_rows < 0 or a missing
+ * rbf_rows: TMDNET_BAD_ARGUMENT, nothing launched. */
 int tmdnet_edge_geom_fwd(int dtype, int n_edges, int num_rbf, int rbf_type, const int32_t* src,
                          const int32_t* dst, const void* deltas, const void* dist, const void* mu,
                          const void* beta, double cutoff_lower, double cutoff_upper, void* rbf,
-                         void* cutoff, void* unit, void* stream);
-/* tmdnet_edge_geom_fwd plus the RBF features of the edges rows[p] into rbf_rows [n_rows][num_rbf]
- * in the same launch (the ET layer stack's pair rows: replaces a gather of rbf). */
-int tmdnet_edge_geom_fwd_rows(int dtype, int n_edges, int num_rbf, int rbf_type, const int32_t* src,
-                              const int32_t* dst, const void* deltas, const void* dist, const void* mu,
-                              const void* beta, double cutoff_lower, double cutoff_upper, void* rbf,
-                              void* cutoff, void* unit, const int32_t* rows, int n_rows, void* rbf_rows,
-                              void* stream);
-/* tmdnet_edge_geom_fwd_rows plus d rbf / d r of the same rows into drbf_rows [n_rows][num_rbf] (the ET
- * force pass's dr-mode operand, formed with the features; replaces a tmdnet_rbf_deriv launch). */
-int tmdnet_edge_geom_fwd_rows2(int dtype, int n_edges, int num_rbf, int rbf_type, const int32_t* src,
-                               const int32_t* dst, const void* deltas, const void* dist, const void* mu,
-                               const void* beta, double cutoff_lower, double cutoff_upper, void* rbf,
-                               void* cutoff, void* unit, const int32_t* rows, int n_rows, void* rbf_rows,
-                               void* drbf_rows, void* stream);
-/* Backward: given grad_rbf [E][R], grad_cutoff [E], grad_unit [E][3] (each nullable) produce
- * grad_dist [E] and grad_deltas [E][3] (both overwritten). */
+                         void* cutoff, void* unit, const int32_t* rows, int n_rows, void* rbf_rows,
+                         void* drbf_rows, void* stream);
 /* Second order of tmdnet_edge_geom_bwd (force-matching training; replaces autograd's double
  * differentiation of reference utils.py:303-390 and the d_ij normalisation, torchmd_et.py:173-174):
  * the VJP of (grad_deltas, grad_dist) for their cotangents gg_deltas [E][3], gg_dist [E] (NULL = 0),
@@ -212,20 +189,17 @@ int tmdnet_edge_geom_bwd2(int dtype, int n_edges, int num_rbf, int rbf_type, con
 int tmdnet_rbf_deriv(int dtype, int num_rbf, int rbf_type, const void* dist, const void* mu,
                      const void* beta, double cutoff_lower, double cutoff_upper, const int32_t* rows,
                      int n_rows, void* out, void* stream);
+/* Backward: given grad_rbf [E][R], grad_cutoff [E], grad_unit [E][3] (each nullable) produce
+ * grad_dist [E] and grad_deltas [E][3] (both overwritten).  The rbf and cutoff outputs take up to three
+ * incoming gradients each (grad_rbf2 / 3, grad_cutoff2 / 3: one per consumer of that output, summed in slot
+ * order in the kernel; NULL slots skipped) -- replaces the autograd engine's add launches for outputs read by
+ * several modules (TensorNet's embedding and interaction layers, tensornet.py:222-230). */
 int tmdnet_edge_geom_bwd(int dtype, int n_edges, int num_rbf, int rbf_type, const int32_t* src,
                          const int32_t* dst, const void* deltas, const void* dist, const void* mu,
-                         const void* beta, double cutoff_lower, double cutoff_upper,
-                         const void* grad_rbf, const void* grad_cutoff, const void* grad_unit,
+                         const void* beta, double cutoff_lower, double cutoff_upper, const void* grad_rbf,
+                         const void* grad_rbf2, const void* grad_rbf3, const void* grad_cutoff,
+                         const void* grad_cutoff2, const void* grad_cutoff3, const void* grad_unit,
                          void* grad_dist, void* grad_deltas, void* stream);
-/* The same with up to three incoming gradients per rbf / cutoff output (one per consumer of that output,
- * summed in slot order in the kernel; NULL slots skipped) -- replaces the autograd engine's add launches
- * for outputs read by several modules (TensorNet's embedding and interaction layers, tensornet.py:222-230). */
-int tmdnet_edge_geom_bwd_multi(int dtype, int n_edges, int num_rbf, int rbf_type, const int32_t* src,
-                               const int32_t* dst, const void* deltas, const void* dist, const void* mu,
-                               const void* beta, double cutoff_lower, double cutoff_upper, const void* grad_rbf,
-                               const void* grad_rbf2, const void* grad_rbf3, const void* grad_cutoff,
-                               const void* grad_cutoff2, const void* grad_cutoff3, const void* grad_unit,
-                               void* grad_dist, void* grad_deltas, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Equivariant-Transformer edge message + aggregation (reference
@@ -300,29 +274,22 @@ int tmdnet_et_message_bwd(int dtype, int n_nodes, int hidden, int heads, const i
  * gg_v [N][3H], gg_vec [N][3][H], gg_pk/gg_pv with leading dimensions).  Outputs: d_grad_x, d_grad_vec,
  * d_q, d_k [N][H], d_v [N][3H], d_vec [N][3][H] (d_k, d_v, d_vec accumulated with atomics: zero them
  * first; d_vec may be NULL when vec_in is NULL), d_pk [E][H], d_pv [E][3H], d_cut [E], d_unit [E][3]
- * (every row written, static-capacity padding rows [row_ptr[n_nodes], max_pairs) with zeros). */
-int tmdnet_et_message_bwd2(int dtype, int n_nodes, int hidden, int heads, const int32_t* row_ptr,
-                           const int32_t* src, int max_pairs, const void* q, int ld_q, const void* k,
-                           int ld_k, const void* v, int ld_v, const void* vec_in, const void* pk,
-                           int ld_pk, const void* pv, int ld_pv, const void* cutoff, const void* unit,
-                           const void* grad_x, const void* grad_vec, const void* gg_q, const void* gg_k,
-                           const void* gg_v, const void* gg_vec, const void* gg_pk, int ld_ggpk,
-                           const void* gg_pv, int ld_ggpv, const void* gg_cut, const void* gg_unit,
-                           void* d_grad_x, void* d_grad_vec, void* d_q, void* d_k, void* d_v,
-                           void* d_vec, void* d_pk, void* d_pv, void* d_cut, void* d_unit, int flags,
-                           void* stream);
-/* tmdnet_et_message_bwd2 with row strides for the node cotangents / outputs (0 = dense) -- so the
- * cotangents can be column blocks of one [N][5H] buffer and d_q | d_k | d_v written into one -- and
- * a DETERMINISTIC source pass: with transpose (the reversed-edge map of tmdnet_nl_build) and
- * edge_scratch ([max_pairs][7][hidden] elements, 16-byte aligned) the source-node terms of every edge
- * are stored as a scratch row and summed per node over the reversed edges by a second kernel (no
- * atomics; d_k, d_v, d_vec are overwritten, no zero fill needed).  transpose / edge_scratch NULL:
- * atomics as tmdnet_et_message_bwd2.  pk_rows (nullable, as in tmdnet_et_message_fwd): edge e's
- * projection rows pk / pv are rows pk_rows[e] (pair-shared rows; gg_pk / gg_pv and d_pk / d_pv stay
- * per edge).  gg_pkv_scale (nullable, needs pk_rows): gg_pk / gg_pv are pair rows too, edge e's
- * cotangent being row pk_rows[e] scaled by gg_pkv_scale[e] (the force-matching second order: the
- * cotangent of the dr-mode g_r times d(dk,dv)/dr).  flags: TMDNET_ET_V_PLANAR | TMDNET_BWD2_ACC_*. */
-int tmdnet_et_message_bwd2_ex(
+ * (every row written, static-capacity padding rows [row_ptr[n_nodes], max_pairs) with zeros).
+ * Optional operands, each 0 / NULL when unused:
+ *   ld_ggq / ld_ggk / ld_ggv, ld_dq / ld_dk / ld_dv, ld_dpk / ld_dpv: row strides of the node cotangents
+ *     and outputs (0 = dense), so the cotangents can be column blocks of one [N][5H] buffer and d_q | d_k |
+ *     d_v written into one.
+ *   transpose (the reversed-edge map of tmdnet_nl_build) with edge_scratch ([max_pairs][7][hidden] elements,
+ *     16-byte aligned), both or neither: a DETERMINISTIC source pass -- the source-node terms of every edge
+ *     are stored as a scratch row and summed per node over the reversed edges by a second kernel (no atomics;
+ *     d_k, d_v, d_vec are overwritten, no zero fill needed).  NULL: the atomics above.
+ *   pk_rows (as in tmdnet_et_message_fwd): edge e's projection rows pk / pv are rows pk_rows[e] (pair-shared
+ *     rows; gg_pk / gg_pv and d_pk / d_pv stay per edge).
+ *   gg_pkv_scale (needs pk_rows): gg_pk / gg_pv are pair rows too, edge e's cotangent being row pk_rows[e]
+ *     scaled by gg_pkv_scale[e] (the force-matching second order: the cotangent of the dr-mode g_r times
+ *     d(dk,dv)/dr).
+ * flags: TMDNET_ET_V_PLANAR | TMDNET_BWD2_ACC_* | the activation bits. */
+int tmdnet_et_message_bwd2(
     int dtype, int n_nodes, int hidden, int heads, const int32_t* row_ptr, const int32_t* src,
     const int32_t* transpose, int max_pairs, const void* q, int ld_q, const void* k, int ld_k,
     const void* v, int ld_v, const void* vec_in, const void* pk, int ld_pk, const void* pv, int ld_pv,
@@ -341,15 +308,12 @@ int tmdnet_et_message_bwd2_ex(
 int tmdnet_et_epilogue_fwd(int dtype, int n_nodes, int hidden, const void* x, const void* vec,
                            const void* vecp, const void* o, const void* vec_agg, void* x_out,
                            void* vec_out, void* stream);
-/* Backward of the epilogue: grad_vecp [N][3][3H], grad_o [N][3H] (x, vec, vec_agg pass through). */
-int tmdnet_et_epilogue_bwd(int dtype, int n_nodes, int hidden, const void* grad_x,
-                           const void* grad_vec, const void* vecp, const void* o, void* grad_vecp,
-                           void* grad_o, void* stream);
-/* tmdnet_et_epilogue_bwd with accumulate != 0: grad_vecp / grad_o are ADDED to (they hold the cotangents
- * the force-loss second order injects; et_stack._backward_layers). */
-int tmdnet_et_epilogue_bwd_acc(int dtype, int n_nodes, int hidden, const void* grad_x, const void* grad_vec,
-                               const void* vecp, const void* o, void* grad_vecp, void* grad_o,
-                               int accumulate, void* stream);
+/* Backward of the epilogue: grad_vecp [N][3][3H], grad_o [N][3H] (x, vec, vec_agg pass through).
+ * accumulate != 0: grad_vecp / grad_o are ADDED to (they hold the cotangents the force-loss second order
+ * injects; et_stack._backward_layers); 0: overwritten. */
+int tmdnet_et_epilogue_bwd(int dtype, int n_nodes, int hidden, const void* grad_x, const void* grad_vec,
+                           const void* vecp, const void* o, void* grad_vecp, void* grad_o, int accumulate,
+                           void* stream);
 
 /* Epilogue of layer l fused with the LayerNorm of layer l+1 (torchmd_et.py:262; biased variance,
  * rstd = 1/sqrt(var + eps), as torch.native_layer_norm).  o == NULL: LayerNorm only (of x; x_out,
@@ -358,24 +322,18 @@ int tmdnet_et_epilogue_ln_fwd(int dtype, int n_nodes, int hidden, const void* x,
                               const void* vecp, const void* o, const void* vec_agg, const void* ln_w,
                               const void* ln_b, double eps, void* x_out, void* vec_out, void* xn,
                               void* mean, void* rstd, void* stream);
-/* grad_x = grad_res + LayerNorm backward of grad_xn (input x, saved mean / rstd, weight ln_w; no
- * weight gradients; grad_res NULL: no residual, e.g. the model's final out_norm); when o != NULL, then the epilogue backward of the previous layer with
- * (grad_x, grad_vec, vecp, o) -> grad_vecp, grad_o (as tmdnet_et_epilogue_bwd; vecp NULL = first
- * layer). */
+/* grad_x = grad_res + grad_res2 + LayerNorm backward of grad_xn (input x, saved mean / rstd, weight ln_w;
+ * grad_res / grad_res2 NULL: no such residual term, e.g. the model's final out_norm); when o != NULL, then the
+ * epilogue backward of the previous layer with (grad_x, grad_vec, vecp, o) -> grad_vecp, grad_o (as
+ * tmdnet_et_epilogue_bwd, accumulate included; vecp NULL = first layer).  w_rows [N][H] (nullable) receives
+ * grad_xn * xhat, the per-row terms of the LayerNorm weight gradient (its column sum; the bias gradient is the
+ * column sum of grad_xn), so a training backward keeps the fused kernel and forms every layer's weight
+ * gradients in one batched reduction (et_stack._backward_layers). */
 int tmdnet_ln_bwd_epilogue(int dtype, int n_nodes, int hidden, const void* grad_xn, const void* x,
                            const void* mean, const void* rstd, const void* ln_w, const void* grad_res,
-                           void* grad_x, const void* grad_vec, const void* vecp, const void* o,
-                           void* grad_vecp, void* grad_o, void* stream);
-/* tmdnet_ln_bwd_epilogue that also writes w_rows [N][H] = grad_xn * xhat, the per-row terms of the
- * LayerNorm weight gradient (its column sum; the bias gradient is the column sum of grad_xn), so a
- * training backward keeps the fused kernel and forms every layer's weight gradients in one batched
- * reduction (et_stack._backward_layers). */
-int tmdnet_ln_bwd_epilogue_w(int dtype, int n_nodes, int hidden, const void* grad_xn, const void* x,
-                             const void* mean, const void* rstd, const void* ln_w, const void* grad_res,
-                             const void* grad_res2, void* grad_x, const void* grad_vec, const void* vecp,
-                             const void* o, void* grad_vecp, void* grad_o, void* w_rows, int accumulate,
-                             void* stream);
-/* (grad_res2: a second residual term, NULL = none; accumulate != 0: grad_vecp / grad_o are ADDED to.) */
+                           const void* grad_res2, void* grad_x, const void* grad_vec, const void* vecp,
+                           const void* o, void* grad_vecp, void* grad_o, void* w_rows, int accumulate,
+                           void* stream);
 
 /* The ET layer's node mixes with the epilogue / LayerNorm pass folded in (et_nodemix.hip; fp32, hidden %
  * 64 == 0, hidden <= 256, 16-byte aligned x_agg / o_w).  Replaces tmdnet_gemm_f32(o_proj) +
@@ -407,27 +365,20 @@ int tmdnet_et_lnbwd_oproj_f32(int n_nodes, int hidden, const void* grad_xn, cons
  * epilogue-backward VJP fused with layer l+1's LayerNorm-backward VJP, one wave per node.
  * Epilogue part (o != NULL): cotangents gb_o [N][3H], gb_vecp [N][3][3H] of tmdnet_et_epilogue_bwd's
  * outputs at (grad_x, grad_vec, vecp, o) -> gbar_x_out = gbar_x_in + its grad_x cotangent,
- * gbar_vec_out = gbar_vec_in (NULL = 0) + its grad_vec cotangent, vecp_bar, o_bar (the primal
- * cotangents); vecp NULL (first layer): only gb_o's third block reaches gbar_x_out.
+ * gbar_vec_out = gbar_vec_in + gbar_vec_in2 (either NULL = 0) + its grad_vec cotangent, vecp_bar, o_bar (the
+ * primal cotangents); vecp NULL (first layer): only gb_o's third block reaches gbar_x_out.  (Two incoming vec
+ * buffers: the force-loss adjoint passes the message VJP's d_gvec beside the running vec cotangent, so no
+ * separate add launch forms their sum.)
  * LayerNorm part (ln_w != NULL): the VJP of g_x = LNB(grad_xn, x) (tmdnet_ln_bwd_epilogue without
  * residual) for the cotangent gbar_x_out (o NULL: gbar_x_in) -> gbar_grad_xn, x_bar, and the per-row
  * products w_bar_rows [N][H] whose column sum is ln_w's cotangent.  mean / rstd as saved by the
  * forward.  Every output written (no accumulation besides the *_in terms). */
 int tmdnet_et_adjoint_epi_ln(int dtype, int n_nodes, int hidden, const void* gb_o, const void* gb_vecp,
                              const void* grad_x, const void* grad_vec, const void* vecp, const void* o,
-                             const void* gbar_x_in, const void* gbar_vec_in, void* gbar_x_out,
-                             void* gbar_vec_out, void* vecp_bar, void* o_bar, const void* x, const void* mean,
-                             const void* rstd, const void* ln_w, const void* grad_xn, void* gbar_grad_xn,
-                             void* x_bar, void* w_bar_rows, void* stream);
-/* The same with the incoming vec cotangent as the sum of two buffers (gbar_vec_in + gbar_vec_in2, either
- * NULL = 0): the force-loss adjoint passes the message VJP's d_gvec beside the running vec cotangent, so no
- * separate add launch forms their sum. */
-int tmdnet_et_adjoint_epi_ln2(int dtype, int n_nodes, int hidden, const void* gb_o, const void* gb_vecp,
-                              const void* grad_x, const void* grad_vec, const void* vecp, const void* o,
-                              const void* gbar_x_in, const void* gbar_vec_in, const void* gbar_vec_in2,
-                              void* gbar_x_out, void* gbar_vec_out, void* vecp_bar, void* o_bar, const void* x,
-                              const void* mean, const void* rstd, const void* ln_w, const void* grad_xn,
-                              void* gbar_grad_xn, void* x_bar, void* w_bar_rows, void* stream);
+                             const void* gbar_x_in, const void* gbar_vec_in, const void* gbar_vec_in2,
+                             void* gbar_x_out, void* gbar_vec_out, void* vecp_bar, void* o_bar, const void* x,
+                             const void* mean, const void* rstd, const void* ln_w, const void* grad_xn,
+                             void* gbar_grad_xn, void* x_bar, void* w_bar_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * EquivariantScalar output head (reference models/output_modules.py:80-115 with two
@@ -630,20 +581,15 @@ int tmdnet_tn_message_fwd(int dtype, int n_nodes, int hidden, const int32_t* row
                           const int32_t* src, int max_pairs, double self0_mult,
                           const int32_t* pad_pairs, int pad_capacity, const void* edge_attr,
                           int ld_ea, const void* comp, void* msg, void* stream);
-/* Backward: g_edge_attr [E][3H] (destination pass), g_comp [9][N][H] (source pass); overwritten. */
+/* Backward: g_edge_attr [E][3H] (destination pass), g_comp [9][N][H] (source pass); overwritten.
+ * g_comp_add ([9][N][H], nullable) is added to g_comp: the gradient the component tensor's other consumer
+ * (TensorNet's decompose(msg Y + Y msg), tensornet.py:398-401) contributes, so the autograd engine does not
+ * sum the two in a separate launch. */
 int tmdnet_tn_message_bwd(int dtype, int n_nodes, int hidden, const int32_t* row_ptr,
                           const int32_t* src, int max_pairs, double self0_mult,
                           const int32_t* pad_pairs, int pad_capacity, const void* edge_attr,
-                          int ld_ea, const void* comp, const void* grad_msg, void* g_edge_attr,
-                          void* g_comp, void* stream);
-/* The same with g_comp_add ([9][N][H], or NULL) added to g_comp: the gradient the component tensor's
- * other consumer (TensorNet's decompose(msg Y + Y msg), tensornet.py:398-401) contributes, so the
- * autograd engine does not sum the two in a separate launch. */
-int tmdnet_tn_message_bwd_add(int dtype, int n_nodes, int hidden, const int32_t* row_ptr,
-                              const int32_t* src, int max_pairs, double self0_mult,
-                              const int32_t* pad_pairs, int pad_capacity, const void* edge_attr,
-                              int ld_ea, const void* comp, const void* grad_msg, const void* g_comp_add,
-                              void* g_edge_attr, void* g_comp, void* stream);
+                          int ld_ea, const void* comp, const void* grad_msg, const void* g_comp_add,
+                          void* g_edge_attr, void* g_comp, void* stream);
 /* Pair-row forms (large systems): the edge factors are functions of |r| only, so the two directions of a
  * pair share one row.  edge_attr / g_edge_attr are [n_pair_slots][3H] in tmdnet_pair_index's numbering
  * (pair_row [E] -> slot, pair_edge [n_pair_slots] -> the slot's canonical edge, src >= dst); edge e reads
@@ -755,16 +701,14 @@ int tmdnet_pair_prior_bwd2(int dtype, int kind, int n_atoms, int n_slots, int n_
 
 /* Scalar head tail fused with the reduction (output_modules.py:83-105, model.py:263-283):
  *   y[b] = *mean + *std * sum_{n: batch[n] = b} (h[n] . w + *b0),  h [n_atoms][K] (ld_h), n_mol <= 8192
- *   (std / mean / b0: device scalars, NULL = 1 / 0 / 0).  Backward: grad_h[n][k] = *std * grad_y[batch[n]] * w[k]. */
+ *   (std / mean / b0: device scalars, NULL = 1 / 0 / 0).  Backward: grad_h[n][k] = *std * grad_y[batch[n]] * w[k].
+ * atom_buf NULL: one workgroup does it all; atom_buf [n_atoms] (large systems): the row products over the
+ * whole grid into it (per-atom h[n].w + b0), then the per-molecule sums. */
 int tmdnet_dot_sum_fwd(int dtype, int n_atoms, int K, const void* h, int ld_h, const void* w, const void* b0,
-                       int n_mol, const int64_t* batch, const void* std_, const void* mean, void* y, void* stream);
+                       int n_mol, const int64_t* batch, const void* std_, const void* mean, void* atom_buf,
+                       void* y, void* stream);
 int tmdnet_dot_sum_bwd(int dtype, int n_atoms, int K, const void* grad_y, const int64_t* batch, int n_mol,
                        const void* std_, const void* w, void* grad_h, void* stream);
-/* The same for large systems: the row products over the whole grid into atom_buf [n_atoms] (per-atom
- * h[n].w + b0), then the per-molecule sums (atom_buf NULL: tmdnet_dot_sum_fwd). */
-int tmdnet_dot_sum_fwd_atoms(int dtype, int n_atoms, int K, const void* h, int ld_h, const void* w, const void* b0,
-                             int n_mol, const int64_t* batch, const void* std_, const void* mean, void* atom_buf,
-                             void* y, void* stream);
 
 /* LayerNorm over the last dimension, fp32, C <= 1024 (reference nn.LayerNorm; TensorNet's init_norm /
  * out_norm, models/tensornet.py:232, 322): y = (x - mean) * rstd * w + b, mean / rstd [rows] saved.
@@ -794,19 +738,15 @@ int tmdnet_layernorm_wgrad_f32(int rows, int C, const void* x, int ldx, const vo
  * = the canonical edge of pair p.  Slots p >= the number of pairs (up to n_pair_slots) and edge
  * slots past *num_pairs (static capacity; num_pairs NULL: row_ptr[n]) get 0.  Requires the
  * transpose map.  sorted_rows != 0 (rows in ascending source order, the brute / shared lists;
- * needs dst) selects a 3-launch closed-form path, else 4 wave-per-row passes.
+ * needs dst) selects a 3-launch closed-form path, else 4 wave-per-row passes.  num_pair_rows[0] (int32 on
+ * the device, nullable) receives the number of pairs numbered, at most n_pair_slots (the same number
+ * tmdnet_nl_build's pair numbering leaves), from the scan launch.
  * Workspace: tmdnet_pair_index_workspace_bytes(n_nodes). */
 size_t tmdnet_pair_index_workspace_bytes(int n_nodes);
 int tmdnet_pair_index(int n_nodes, const int32_t* row_ptr, const int32_t* src, const int32_t* dst,
                       const int32_t* transpose, int max_pairs, const int32_t* num_pairs, int sorted_rows,
-                      int32_t* pair_row, int32_t* pair_edge, int n_pair_slots, void* workspace,
-                      size_t workspace_bytes, void* stream);
-/* tmdnet_pair_index that also writes num_pair_rows[0] (int32 on the device, nullable) = the number of pairs
- * numbered, at most n_pair_slots (the same number tmdnet_nl_build_paired_rows leaves), from its scan launch. */
-int tmdnet_pair_index_rows(int n_nodes, const int32_t* row_ptr, const int32_t* src, const int32_t* dst,
-                           const int32_t* transpose, int max_pairs, const int32_t* num_pairs, int sorted_rows,
-                           int32_t* pair_row, int32_t* pair_edge, int n_pair_slots, int32_t* num_pair_rows,
-                           void* workspace, size_t workspace_bytes, void* stream);
+                      int32_t* pair_row, int32_t* pair_edge, int n_pair_slots, int32_t* num_pair_rows,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* Grouped small fp32 GEMM on the f32 MFMA (node feature mixes of the ET layer, torchmd_et.py:272-312):
  * up to 4 independent problems in one launch.  Problem i: dims[8i..8i+7] = {M, N, K, lda, ldb, ldc,
@@ -872,28 +812,31 @@ int tmdnet_embedding_bwd_f32(int n, int H, int num_types, const int64_t* z, int 
  * orders sum to <= 2 are accumulated in fp32 -- fp32 GEMM accuracy (not a bf16 result).  Requirements:
  * K = 32 or 64 (split: K % 4 == 0), N % 16 == 0, lda / ldc multiples of 4, 16-byte aligned A / Wp / C /
  * bias; else TMDNET_UNSUPPORTED (callers use the library GEMM).  Replaces the nn.Linear of
- * torchmd_et.py:287-288 over the edges. */
+ * torchmd_et.py:287-288 over the edges.
+ * rows (int32 on the device, 4-byte aligned, nullable): the live row count of a static-capacity buffer, read
+ * by the kernel -- no host sync, so a captured step follows the count of each replay.  It takes effect as
+ * min(M, max(0, *rows)).  Rows below it are bit-identical to the launch without rows; ROWS AT OR PAST IT ARE
+ * NOT WRITTEN (C keeps whatever the buffer held), so every reader must be index-driven or row-counted itself.
+ * Row tiles past the count leave without a store or an MFMA.  rows NULL: every row. */
 /* Large-row fp32 GEMMs at fp32 accuracy on the bf16 MFMA (the node feature mixes of C5-size systems:
  * EquivariantMultiHeadAttention q/k/v, vec_proj, o_proj Linears and their input gradients,
  * reference torchmd_et.py:273-278, 309; the NeighborEmbedding distance_proj, models/utils.py:98-103):
  *   tmdnet_split_t_f32: Bp [3][N][K] = the exact bf16 pieces of B^T for a [K][N] right operand (ldb);
  *     (a [N][K] Linear weight is split by tmdnet_proj_split_f32);
  *   tmdnet_gemm_x3_f32: C [M][N] = beta C + A [M][K] Bp^T + bias (nullable) -- K % 32 == 0, N % 16 == 0,
- *     16-byte aligned rows / pointers, otherwise TMDNET_UNSUPPORTED (nothing launched). */
+ *     16-byte aligned rows / pointers, otherwise TMDNET_UNSUPPORTED (nothing launched).  Its epilogue is
+ *     tmdnet_gemm_ex_f32's, every part optional (act 0, pointers NULL, ldx 0), for the Linear + SiLU stacks of
+ *     large systems (TensorNet's edge MLP, reference tensornet.py:381-385, over ~1M pair rows at C5; the
+ *     embedding's scalar MLP tensornet.py:320-321): v = acc + bias (+ C if beta) -> pre[r][c] = v -> v =
+ *     silu(v) if act -> v *= rscale[r] -> v *= silu'(dpre[r][c]) -> C.  pre / dpre: row stride ldx (>= N,
+ *     % 4), 16-byte aligned. */
 int tmdnet_split_t_f32(int N, int K, const void* B, int ldb, void* Bp, void* stream);
 int tmdnet_gemm_x3_f32(int M, int N, int K, const void* A, int lda, const void* Bp, const void* bias, void* C,
-                       int ldc, int beta, void* stream);
-/* tmdnet_gemm_x3_f32 with tmdnet_gemm_ex_f32's epilogue, for the Linear + SiLU stacks of large systems
- * (TensorNet's edge MLP, reference tensornet.py:381-385, over ~1M pair rows at C5; the embedding's scalar
- * MLP tensornet.py:320-321): v = acc + bias (+ C if beta) -> pre[r][c] = v (nullable) -> v = silu(v) if act
- * -> v *= rscale[r] (nullable) -> v *= silu'(dpre[r][c]) (nullable) -> C.  pre / dpre: row stride ldx
- * (>= N, % 4), 16-byte aligned. */
-int tmdnet_gemm_x3_ex_f32(int M, int N, int K, const void* A, int lda, const void* Bp, const void* bias, void* C,
-                          int ldc, int beta, int act, void* pre, const void* rscale, const void* dpre, int ldx,
-                          void* stream);
+                       int ldc, int beta, int act, void* pre, const void* rscale, const void* dpre, int ldx,
+                       void* stream);
 int tmdnet_proj_split_f32(int N, int K, const void* W, int ldw, void* Wp, void* stream);
 int tmdnet_proj_f32(int M, int N, int K, const void* A, int lda, const void* Wp, long long piece_stride,
-                    const void* bias, void* C, int ldc, void* stream);
+                    const void* bias, void* C, int ldc, const int32_t* rows, void* stream);
 /* tmdnet_proj_f32 with the dk / dv activation in the GEMM's epilogue -- the rows the ET message kernels read
  * under TMDNET_ET_PREACT.  With pre = A W^T + bias (the bits tmdnet_proj_f32 writes: same split, same
  * accumulation order):
@@ -901,21 +844,11 @@ int tmdnet_proj_f32(int M, int N, int K, const void* A, int lda, const void* Wp,
  *   D [M][N] = act'(pre) * (dA W^T)              (dA, D nullable together: dA = d A / d r at the same rows,
  *                                                 row stride lda; no bias on the derivative)
  * S and D share the row stride ldc.  Envelope and alignment as tmdnet_proj_f32 (else TMDNET_UNSUPPORTED,
- * nothing launched; dA and D 16-byte aligned too); D without dA, or an unknown act: TMDNET_BAD_ARGUMENT. */
+ * nothing launched; dA and D 16-byte aligned too); D without dA, or an unknown act: TMDNET_BAD_ARGUMENT.
+ * rows: the live row count, exactly as tmdnet_proj_f32's (rows of S and D at or past it are not written). */
 int tmdnet_proj_act_f32(int M, int N, int K, const void* A, const void* dA, int lda, const void* Wp,
                         long long piece_stride, const void* bias, int act, void* S, void* D, int ldc,
-                        void* stream);
-/* The two projections over the live rows of a static-capacity buffer: rows (int32 on the device, 4-byte
- * aligned, nullable) holds the row count, read by the kernel -- no host sync, so a captured step follows the
- * count of each replay.  It takes effect as min(M, max(0, *rows)).  Rows below it are bit-identical to the
- * launch without rows; ROWS AT OR PAST IT ARE NOT WRITTEN (C / S / D keep whatever the buffer held), so every
- * reader must be index-driven or row-counted itself.  Row tiles past the count leave without a store or an
- * MFMA.  rows NULL: tmdnet_proj_f32 / tmdnet_proj_act_f32.  Same argument checks and return codes. */
-int tmdnet_proj_rows_f32(int M, int N, int K, const void* A, int lda, const void* Wp, long long piece_stride,
-                         const void* bias, void* C, int ldc, const int32_t* rows, void* stream);
-int tmdnet_proj_act_rows_f32(int M, int N, int K, const void* A, const void* dA, int lda, const void* Wp,
-                             long long piece_stride, const void* bias, int act, void* S, void* D, int ldc,
-                             const int32_t* rows, void* stream);
+                        const int32_t* rows, void* stream);
 
 /* The ET message with the dk/dv projection FUSED in (reference torchmd_et.py:282-291 + :314-347, the
  * RBF of models/utils.py:272-344): tmdnet_et_message_fwd's outputs without the projection rows.  Per

@@ -170,7 +170,7 @@ def _fake_epi_ln(x, vec, vecp, o, veca, ln_w, ln_b, xn_out=None, vo_out=None):
 
 def _fake_ln_bwd_epi(g_xn, x, mean, rstd, ln_w, g_res, g_vec, vecp, o, g_vecp, g_o, wrows=None, g_res2=None,
                      acc=False):
-    """tmdnet_ln_bwd_epilogue_w restated: residual + LayerNorm backward, then the previous epilogue
+    """tmdnet_ln_bwd_epilogue restated: residual + LayerNorm backward, then the previous epilogue
     (and the LayerNorm weight gradient's row terms)."""
     g_x, _, _ = torch.ops.aten.native_layer_norm_backward(g_xn, x, [x.shape[1]], mean, rstd, ln_w, None,
                                                           [True, False, False])
@@ -203,7 +203,7 @@ def _fake_bwd2(ctx, ggs):
 
 def _fake_bwd2_launch(q, k, v, vec, pk, pv, C, u, graph, heads, gx, gvec, ggs, flags=0, out=None, pk_rows=None,
                       gg_pkv_scale=None):
-    """tmdnet_et_message_bwd2_ex restated: the VJP of the message backward by double autograd (``out``
+    """tmdnet_et_message_bwd2 restated: the VJP of the message backward by double autograd (``out``
     buffers filled / accumulated as the launch wrapper does; ``pk_rows``: pair-shared projection rows;
     ``gg_pkv_scale``: the projection cotangents are pair rows scaled per edge)."""
     if gg_pkv_scale is not None:

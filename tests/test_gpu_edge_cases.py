@@ -144,7 +144,7 @@ def test_gated_eq_gradients_isolated_atom():
 @pytest.mark.parametrize("dtype,tol", [(torch.float64, 1e-11), (torch.float32, 2e-5)])
 @pytest.mark.parametrize("slots", [1, 3])
 def test_edge_geometry_backward_matches_autograd(R, rbf, dtype, tol, slots):
-    """tmdnet_edge_geom_bwd_multi (the lane-parallel k_bwd_v: R = 16 / 32 / 64; R = 50 takes the
+    """tmdnet_edge_geom_bwd (the lane-parallel k_bwd_v: R = 16 / 32 / 64; R = 50 takes the
     wave-per-edge form) against autograd of the formulas (reference models/utils.py:272-390, the unit
     vectors torchmd_et.py:173-174): g_r and g_deltas for 1 or 3 gradient slots of rbf and cutoff, with
     self loops and a lower cutoff."""

@@ -511,7 +511,7 @@ def test_static_capacity_matches_dynamic_graph(dtype):
 
 # ----------------------------------------------------------------------------- 7. second order
 def _second_order_case(rep, H, heads, dtype, mode, monkeypatch):
-    """_ETMessageBwd differentiated (tmdnet_et_message_bwd2_ex) against double autograd through the composite,
+    """_ETMessageBwd differentiated (tmdnet_et_message_bwd2) against double autograd through the composite,
     all ten inputs; ``mode``: "scratch" / "atomic" source pass, or "pairs" (the launch with pk_rows)."""
     from torchmdnet import kernels
     if mode == "atomic":
@@ -564,7 +564,7 @@ def test_message_second_order_across_widths(H, dtype, mode, monkeypatch):
 
 @pytest.mark.parametrize("dtype", [F32, F64], ids=["f32", "f64"])
 def test_message_second_order_with_pair_rows(dtype, monkeypatch):
-    """tmdnet_et_message_bwd2_ex reading pair-shared projection rows through pk_rows, H = 128."""
+    """tmdnet_et_message_bwd2 reading pair-shared projection rows through pk_rows, H = 128."""
     rep = _Report("message-2nd")
     _second_order_case(rep, 128, 8, dtype, "pairs", monkeypatch)
     rep.done()

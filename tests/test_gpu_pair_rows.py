@@ -1,8 +1,8 @@
 """The device pair-row count of a static-capacity graph (``EdgeGraph.num_pair_rows_dev``) and the captured ET
 evaluation that stops its dk/dv projection there (et_stack: ``proj_act(..., rows=)``).
 
-The count: written by the neighbour build's row scan (``tmdnet_nl_build_paired_rows``) or by the pair numbering's
-scan (``tmdnet_pair_index_rows``); both must leave the number of pairs numbered over the KEPT list -- the number
+The count: written by the neighbour build's row scan (``tmdnet_nl_build``'s ``num_pair_rows``) or by the pair numbering's
+scan (``tmdnet_pair_index``'s); both must leave the number of pairs numbered over the KEPT list -- the number
 of distinct ``pair_row`` values of the live edges, every one of them below it -- clamped to the slot count, with
 head room in the capacity and with a capacity that truncates the list.
 

@@ -762,7 +762,7 @@ def test_graphed_tensornet_matches_eager(static_shapes):
 @pytest.mark.parametrize("src_pass", ["deterministic", "atomic"])
 @pytest.mark.parametrize("infl", ["both", "none"])
 def test_et_message_second_order_kernel_matches_composite(infl, src_pass, monkeypatch):
-    """tmdnet_et_message_bwd2_ex (the VJP of the HIP first backward) == double backward through the
+    """tmdnet_et_message_bwd2 (the VJP of the HIP first backward) == double backward through the
     PyTorch restatement, fp64, all ten inputs (gx, gvec, q, k, v, vec, pk, pv, C, u); the source-node
     terms summed by the scratch-row source pass over the reversed edges, or by atomics."""
     from torchmdnet import kernels
@@ -1102,7 +1102,7 @@ def test_pair_index_matches_composite(static):
             graph._pairs, graph.sorted_rows = None, False
             pr2, pe2 = kernels.pair_index(graph)
             assert torch.equal(pr, pr2) and torch.equal(pe, pe2)
-            # == the numbering produced inside the build (tmdnet_nl_build_paired)
+            # == the numbering produced inside the build (tmdnet_nl_build's pair operands)
             fg = kernels.build_graph(pos, batch, 0.0, 5.0, 128 * n, loop=True, strategy=strat, box=box,
                                      static_capacity=(None if not static else 96 * n), pairs=True)
             fr, fe = fg._pairs

@@ -1,11 +1,11 @@
-"""The row-counted dk/dv projections (``tmdnet_proj_rows_f32`` / ``tmdnet_proj_act_rows_f32``, csrc/gemm.hip
+"""The row-counted dk/dv projections (the ``rows`` operand of ``tmdnet_proj_f32`` / ``tmdnet_proj_act_f32``, csrc/gemm.hip
 ``tmd::proj``): with an int32 device row count the kernels write the rows below ``min(M, max(0, count))`` only.
 
 Contract checked here, all as int32 bit patterns (no tolerance anywhere):
   * rows below the effective count == the same call without a count (same tiles, split, order, epilogue);
   * rows at or past it keep the sentinel the output was pre-filled with (no store at all), as do the guard
     columns of a wider buffer (``ldc > N``: S / D are column slices of one buffer in the model);
-  * a null count through the new entry points == the old entry points.
+  * a null count == the uncounted launch, through the C ABI.
 Shapes: K = 32 and 64, a whole and a partial 64-column tile (N = 64, 80), M = 160 = one whole and one partial
 128-row tile, with and without dA / D; counts on every side of the 16-row block, the 128-row tile and M, plus the
 two clamps (165 > M, -3 < 0); the 256-row tiles from M = 65536.
@@ -110,8 +110,8 @@ def test_rows_large_tiles(kind, K):
 
 
 def test_null_rows_equal_the_old_entry_points():
-    """tmdnet_proj_rows_f32 / tmdnet_proj_act_rows_f32 with rows = NULL against tmdnet_proj_f32 /
-    tmdnet_proj_act_f32, through the C ABI."""
+    """tmdnet_proj_f32 / tmdnet_proj_act_f32 through the C ABI, with a device row count against rows = NULL (the
+    uncounted launch): rows below the count are the same bits, rows at or past it are not written."""
     from torchmdnet import _native as nat
     from torchmdnet import kernels
     lib = nat.load()
@@ -120,27 +120,31 @@ def test_null_rows_equal_the_old_entry_points():
         A, dA, W, b = _operands(M, N, K)
         wp = kernels.proj_split(W)
         st = nat.stream(A.device)
-        old, _ = _filled(M, N)
-        new, _ = _filled(M, N)
-        common = (M, N, K, nat.ptr(A), K, nat.ptr(wp), N * K, nat.ptr(b))
-        nat.check(lib.tmdnet_proj_f32(*common, nat.ptr(old), N, st), "tmdnet_proj_f32")
-        nat.check(lib.tmdnet_proj_rows_f32(*common, nat.ptr(new), N, None, st), "tmdnet_proj_rows_f32")
-        assert torch.equal(_bits(old), _bits(new)) and not bool((_bits(new) == SENTINEL).any())
-        for der in (False, True):
-            outs = [[_filled(M, N)[0] for _ in range(2)] for _ in range(2)]
-            common = (M, N, K, nat.ptr(A), nat.ptr(dA) if der else None, K, nat.ptr(wp), N * K, nat.ptr(b), 0)
-            (So, Do), (Sn, Dn) = outs
-            nat.check(lib.tmdnet_proj_act_f32(*common, nat.ptr(So), nat.ptr(Do) if der else None, N, st),
-                      "tmdnet_proj_act_f32")
-            nat.check(lib.tmdnet_proj_act_rows_f32(*common, nat.ptr(Sn), nat.ptr(Dn) if der else None, N, None, st),
-                      "tmdnet_proj_act_rows_f32")
-            assert torch.equal(_bits(So), _bits(Sn)) and torch.equal(_bits(Do), _bits(Dn))
-            assert not bool((_bits(Sn) == SENTINEL).any())
-            assert bool((_bits(Dn) == SENTINEL).any()) != der
+        for c in (M, M - 37):
+            rows = torch.tensor([c], dtype=torch.int32, device=DEV)
+            old, _ = _filled(M, N)
+            new, _ = _filled(M, N)
+            common = (M, N, K, nat.ptr(A), K, nat.ptr(wp), N * K, nat.ptr(b))
+            nat.check(lib.tmdnet_proj_f32(*common, nat.ptr(old), N, None, st), "tmdnet_proj_f32")
+            nat.check(lib.tmdnet_proj_f32(*common, nat.ptr(new), N, nat.ptr(rows), st), "tmdnet_proj_f32")
+            assert not bool((_bits(old) == SENTINEL).any())
+            assert torch.equal(_bits(old)[:c], _bits(new)[:c]) and bool((_bits(new)[c:] == SENTINEL).all())
+            for der in (False, True):
+                outs = [[_filled(M, N)[0] for _ in range(2)] for _ in range(2)]
+                common = (M, N, K, nat.ptr(A), nat.ptr(dA) if der else None, K, nat.ptr(wp), N * K, nat.ptr(b), 0)
+                (So, Do), (Sn, Dn) = outs
+                nat.check(lib.tmdnet_proj_act_f32(*common, nat.ptr(So), nat.ptr(Do) if der else None, N, None, st),
+                          "tmdnet_proj_act_f32")
+                nat.check(lib.tmdnet_proj_act_f32(*common, nat.ptr(Sn), nat.ptr(Dn) if der else None, N,
+                                                  nat.ptr(rows), st), "tmdnet_proj_act_f32")
+                assert torch.equal(_bits(So)[:c], _bits(Sn)[:c]) and torch.equal(_bits(Do)[:c], _bits(Dn)[:c])
+                assert not bool((_bits(So) == SENTINEL).any())
+                assert bool((_bits(Sn)[c:] == SENTINEL).all()) and bool((_bits(Dn)[c:] == SENTINEL).all())
+                assert bool((_bits(Do) == SENTINEL).any()) != der
 
 
 def test_rows_argument_checks():
-    """The new entry points keep the old ones' argument checks; a misaligned count pointer is refused."""
+    """The argument checks hold with a row count given; a misaligned count pointer is refused."""
     from torchmdnet import _native as nat
     from torchmdnet import kernels
     lib = nat.load()
@@ -151,12 +155,12 @@ def test_rows_argument_checks():
     st = nat.stream(A.device)
     import ctypes
     odd = ctypes.c_void_p(rows.data_ptr() + 2)
-    assert lib.tmdnet_proj_rows_f32(M0, 64, 64, nat.ptr(A), 64, nat.ptr(wp), 64 * 64, nat.ptr(b), nat.ptr(out), 64,
-                                    odd, st) == kernels.GEMM_UNSUPPORTED
-    assert lib.tmdnet_proj_rows_f32(M0, 64, 48, nat.ptr(A), 64, nat.ptr(wp), 64 * 64, nat.ptr(b), nat.ptr(out), 64,
-                                    nat.ptr(rows), st) == kernels.GEMM_UNSUPPORTED
-    assert lib.tmdnet_proj_act_rows_f32(M0, 64, 64, nat.ptr(A), None, 64, nat.ptr(wp), 64 * 64, nat.ptr(b), 0,
-                                        nat.ptr(out), nat.ptr(out), 64, nat.ptr(rows), st) != 0  # D without dA
+    assert lib.tmdnet_proj_f32(M0, 64, 64, nat.ptr(A), 64, nat.ptr(wp), 64 * 64, nat.ptr(b), nat.ptr(out), 64,
+                               odd, st) == kernels.GEMM_UNSUPPORTED
+    assert lib.tmdnet_proj_f32(M0, 64, 48, nat.ptr(A), 64, nat.ptr(wp), 64 * 64, nat.ptr(b), nat.ptr(out), 64,
+                               nat.ptr(rows), st) == kernels.GEMM_UNSUPPORTED
+    assert lib.tmdnet_proj_act_f32(M0, 64, 64, nat.ptr(A), None, 64, nat.ptr(wp), 64 * 64, nat.ptr(b), 0,
+                                   nat.ptr(out), nat.ptr(out), 64, nat.ptr(rows), st) != 0  # D without dA
     assert bool((_bits(out) == SENTINEL).all())  # nothing was launched
     with pytest.raises(RuntimeError):
         kernels.proj(A, W, b, rows=torch.zeros(1, dtype=torch.int64, device=DEV))

@@ -1,7 +1,7 @@
 """The per-molecule virial (tmdnet_nl_backward_virial, TorchMD_Net.energy_forces_virial) on the GPU.
 
 Kernel level: against ``kernels.nl_backward_virial_composite`` evaluated in float64 on upcast inputs, with
-``grad_pos`` bitwise equal to tmdnet_nl_backward_multi's.  Model level: against the exact strain derivative of
+``grad_pos`` bitwise equal to tmdnet_nl_backward's.  Model level: against the exact strain derivative of
 the fp64 oracle (tests/virial_ref.py) on the reference-run periodic fixtures, and against
 ``sum_i neg_dy_i (x) pos_i`` for isolated molecules.
 
@@ -86,10 +86,10 @@ def _multi(pos, gd, gr, gr2, dl, dist, graph):
     from torchmdnet import _native as nat
     lib = nat.load()
     gpos = torch.empty_like(pos)
-    rc = lib.tmdnet_nl_backward_multi(nat.dtype_code(pos.dtype), pos.shape[0], nat.ptr(graph.row_ptr),
-                                      nat.ptr(graph.transpose), graph.n_edges, nat.ptr(gd), nat.ptr(gr), nat.ptr(gr2),
-                                      nat.ptr(dl), nat.ptr(dist), nat.ptr(gpos), nat.stream(pos.device))
-    nat.check(rc, "tmdnet_nl_backward_multi")
+    rc = lib.tmdnet_nl_backward(nat.dtype_code(pos.dtype), pos.shape[0], nat.ptr(graph.row_ptr),
+                                nat.ptr(graph.transpose), graph.n_edges, nat.ptr(gd), nat.ptr(gr), nat.ptr(gr2),
+                                nat.ptr(dl), nat.ptr(dist), nat.ptr(gpos), nat.stream(pos.device))
+    nat.check(rc, "tmdnet_nl_backward")
     return gpos
 
 
@@ -131,7 +131,7 @@ def _kernel_case(pos64, batch, loop, static, which, dtype, box=None, need_shift=
     ref_gpos = _multi(pos, gd, gr, gr2, dl, dist, graph)
     gpos, w = kernels.nl_backward_virial(pos, gd, gr, gr2, dl, dist, graph, batch, n_mol)
     torch.cuda.synchronize()
-    assert torch.equal(gpos, ref_gpos), "grad_pos differs from tmdnet_nl_backward_multi"
+    assert torch.equal(gpos, ref_gpos), "grad_pos differs from tmdnet_nl_backward"
     up = lambda t: None if t is None else t[:E].double()
     ref = kernels.nl_backward_virial_composite(up(gd), up(gr), up(gr2), dl[:E].double(), dist[:E].double(),
                                                graph.dst[:E], batch, n_mol)
@@ -149,7 +149,7 @@ SETS = [("gd",), ("gr",), ("gr", "gr2"), ("gd", "gr", "gr2")]
 @pytest.mark.parametrize("loop", [True, False], ids=["loop", "noloop"])
 def test_kernel_against_composite(loop, which, dtype):
     """Dynamic list and static capacity (NaN in every padding row) on the same input: each against the float64
-    composite, grad_pos bitwise tmdnet_nl_backward_multi's, and the two forms agree with each other."""
+    composite, grad_pos bitwise tmdnet_nl_backward's, and the two forms agree with each other."""
     pos, batch = _atoms()
     g_dyn, w_dyn = _kernel_case(pos, batch, loop, False, set(which), dtype)
     g_st, w_st = _kernel_case(pos, batch, loop, True, set(which), dtype)

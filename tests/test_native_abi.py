@@ -30,8 +30,7 @@ def test_header_declares_entry_points():
                  "tmdnet_nbr_embed_bwd", "tmdnet_tn_embed_fwd", "tmdnet_tn_embed_bwd",
                  "tmdnet_tn_message_fwd", "tmdnet_tn_message_bwd", "tmdnet_tn_node_fwd", "tmdnet_tn_node_bwd", "tmdnet_silu_fwd", "tmdnet_silu_bwd",
                  "tmdnet_atom_sum_fwd", "tmdnet_atom_sum_bwd", "tmdnet_gemm_f32", "tmdnet_pair_index",
-                 "tmdnet_rbf_deriv", "tmdnet_nl_build_paired",
-                 "tmdnet_edge_geom_fwd_rows",
+                 "tmdnet_rbf_deriv",
                  "tmdnet_nl_workspace_bytes",
                  "tmdnet_build_info"):
         assert name in d, name
@@ -54,6 +53,30 @@ def test_ctypes_table_matches_header_arity():
     assert set(d) == set(_native.SIGNATURES)
     for name, args in d.items():
         assert len(_native.SIGNATURES[name][1]) == len(args), name
+
+
+# the suffixed variants folded into their base names (one exported name per kernel family; optional operands
+# are NULL / 0 on the base name)
+FOLDED = ("tmdnet_nl_build_paired", "tmdnet_nl_build_paired_rows", "tmdnet_nl_backward_multi",
+          "tmdnet_edge_geom_fwd_rows", "tmdnet_edge_geom_fwd_rows2", "tmdnet_edge_geom_bwd_multi",
+          "tmdnet_et_message_bwd2_ex", "tmdnet_et_epilogue_bwd_acc", "tmdnet_ln_bwd_epilogue_w",
+          "tmdnet_et_adjoint_epi_ln2", "tmdnet_tn_message_bwd_add", "tmdnet_pair_index_rows",
+          "tmdnet_proj_rows_f32", "tmdnet_proj_act_rows_f32", "tmdnet_dot_sum_fwd_atoms", "tmdnet_gemm_x3_ex_f32")
+
+
+def test_folded_names_are_gone():
+    from torchmdnet import _native
+    assert len(set(FOLDED)) == 16
+    words = set(re.findall(r"\w+", open(HEADER).read()))  # comments included
+    for name in FOLDED:
+        assert name not in words, name
+        assert name not in _native.SIGNATURES, name
+
+
+def test_signature_table_size():
+    """108 entries before the suffixed variants were folded, sixteen fewer after."""
+    from torchmdnet import _native
+    assert len(_native.SIGNATURES) == 108 - 16
 
 
 def test_library_is_gfx950_code_object():

@@ -1,4 +1,4 @@
-"""Isolated timing of the x3 GEMM (kernels.gemm_ex_launch above GEMM_MAX_ROWS -> tmdnet_gemm_x3_ex_f32) at the
+"""Isolated timing of the x3 GEMM (kernels.gemm_ex_launch above GEMM_MAX_ROWS -> tmdnet_gemm_x3_f32) at the
 C5 TensorNet shapes: the pair-row edge MLP (P ~ 1.0M rows: 32 -> 128 -> 256 -> 384 with the SiLU / pre /
 cutoff epilogues; the backward's input gradients with the silu' epilogue) and the embedding's distance
 projection over the edges (E ~ 1.96M, 32 -> 384).  us per call, bytes (A + epilogue operands + outputs) / time,

@@ -412,10 +412,13 @@ static Cfg<T> make(int E, int R, int type, const int32_t* src, const int32_t* ds
 
 using namespace tmd;
 
-static int geom_fwd(int dtype, int n_edges, int num_rbf, int rbf_type, const int32_t* src, const int32_t* dst,
-                    const void* deltas, const void* dist, const void* mu, const void* beta, double cutoff_lower,
-                    double cutoff_upper, void* rbf, void* cutoff, void* unit, const int32_t* rows, int n_rows,
-                    void* rbf_rows, void* drbf_rows, void* stream) {
+extern "C" int tmdnet_edge_geom_fwd(int dtype, int n_edges, int num_rbf, int rbf_type, const int32_t* src,
+                                    const int32_t* dst, const void* deltas, const void* dist, const void* mu,
+                                    const void* beta, double cutoff_lower, double cutoff_upper, void* rbf,
+                                    void* cutoff, void* unit, const int32_t* rows, int n_rows, void* rbf_rows,
+                                    void* drbf_rows, void* stream) {
+  // no rows: no row operand at all; rows: their features are wanted, the derivatives optional
+  if (rows ? (n_rows < 0 || (n_rows > 0 && !rbf_rows)) : (n_rows != 0 || rbf_rows || drbf_rows)) return kBadArgument;
   if (n_edges <= 0) return kOk;
   hipStream_t st = (hipStream_t)stream;
   long long work = rbf ? (long long)n_edges * num_rbf : n_edges;
@@ -436,44 +439,12 @@ static int geom_fwd(int dtype, int n_edges, int num_rbf, int rbf_type, const int
   return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
 }
 
-extern "C" int tmdnet_edge_geom_fwd(int dtype, int n_edges, int num_rbf, int rbf_type,
-                                    const int32_t* src, const int32_t* dst, const void* deltas,
-                                    const void* dist, const void* mu, const void* beta,
-                                    double cutoff_lower, double cutoff_upper, void* rbf, void* cutoff,
-                                    void* unit, void* stream) {
-  return geom_fwd(dtype, n_edges, num_rbf, rbf_type, src, dst, deltas, dist, mu, beta, cutoff_lower, cutoff_upper,
-                  rbf, cutoff, unit, nullptr, 0, nullptr, nullptr, stream);
-}
-
-extern "C" int tmdnet_edge_geom_fwd_rows(int dtype, int n_edges, int num_rbf, int rbf_type,
-                                         const int32_t* src, const int32_t* dst, const void* deltas,
-                                         const void* dist, const void* mu, const void* beta,
-                                         double cutoff_lower, double cutoff_upper, void* rbf, void* cutoff,
-                                         void* unit, const int32_t* rows, int n_rows, void* rbf_rows,
-                                         void* stream) {
-  if (!rows || n_rows < 0 || (n_rows > 0 && !rbf_rows)) return kBadArgument;
-  return geom_fwd(dtype, n_edges, num_rbf, rbf_type, src, dst, deltas, dist, mu, beta, cutoff_lower, cutoff_upper,
-                  rbf, cutoff, unit, rows, n_rows, rbf_rows, nullptr, stream);
-}
-
-extern "C" int tmdnet_edge_geom_fwd_rows2(int dtype, int n_edges, int num_rbf, int rbf_type,
-                                          const int32_t* src, const int32_t* dst, const void* deltas,
-                                          const void* dist, const void* mu, const void* beta,
-                                          double cutoff_lower, double cutoff_upper, void* rbf, void* cutoff,
-                                          void* unit, const int32_t* rows, int n_rows, void* rbf_rows,
-                                          void* drbf_rows, void* stream) {
-  if (!rows || n_rows < 0 || (n_rows > 0 && (!rbf_rows || !drbf_rows))) return kBadArgument;
-  return geom_fwd(dtype, n_edges, num_rbf, rbf_type, src, dst, deltas, dist, mu, beta, cutoff_lower, cutoff_upper,
-                  rbf, cutoff, unit, rows, n_rows, rbf_rows, drbf_rows, stream);
-}
-
-extern "C" int tmdnet_edge_geom_bwd_multi(int dtype, int n_edges, int num_rbf, int rbf_type,
-                                          const int32_t* src, const int32_t* dst, const void* deltas,
-                                          const void* dist, const void* mu, const void* beta,
-                                          double cutoff_lower, double cutoff_upper, const void* grad_rbf,
-                                          const void* grad_rbf2, const void* grad_rbf3, const void* grad_cutoff,
-                                          const void* grad_cutoff2, const void* grad_cutoff3, const void* grad_unit,
-                                          void* grad_dist, void* grad_deltas, void* stream) {
+extern "C" int tmdnet_edge_geom_bwd(int dtype, int n_edges, int num_rbf, int rbf_type, const int32_t* src,
+                                    const int32_t* dst, const void* deltas, const void* dist, const void* mu,
+                                    const void* beta, double cutoff_lower, double cutoff_upper, const void* grad_rbf,
+                                    const void* grad_rbf2, const void* grad_rbf3, const void* grad_cutoff,
+                                    const void* grad_cutoff2, const void* grad_cutoff3, const void* grad_unit,
+                                    void* grad_dist, void* grad_deltas, void* stream) {
   if (n_edges <= 0) return kOk;
   hipStream_t st = (hipStream_t)stream;
   const int tb = 256;
@@ -510,17 +481,6 @@ extern "C" int tmdnet_edge_geom_bwd_multi(int dtype, int n_edges, int num_rbf, i
     return kUnsupported;
 #undef TMD_GEOM_BWD
   return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
-}
-
-extern "C" int tmdnet_edge_geom_bwd(int dtype, int n_edges, int num_rbf, int rbf_type,
-                                    const int32_t* src, const int32_t* dst, const void* deltas,
-                                    const void* dist, const void* mu, const void* beta,
-                                    double cutoff_lower, double cutoff_upper, const void* grad_rbf,
-                                    const void* grad_cutoff, const void* grad_unit, void* grad_dist,
-                                    void* grad_deltas, void* stream) {
-  return tmdnet_edge_geom_bwd_multi(dtype, n_edges, num_rbf, rbf_type, src, dst, deltas, dist, mu, beta,
-                                    cutoff_lower, cutoff_upper, grad_rbf, nullptr, nullptr, grad_cutoff, nullptr,
-                                    nullptr, grad_unit, grad_dist, grad_deltas, stream);
 }
 
 extern "C" int tmdnet_rbf_deriv(int dtype, int num_rbf, int rbf_type, const void* dist, const void* mu,

@@ -1822,7 +1822,7 @@ static int bwd(int n, int H, int heads, const int32_t* row_ptr, const int32_t* s
   return et_launch<T, 2, false>(V, A, st);
 }
 
-struct Bwd2Ex {  // the strides / accumulation / source-pass extras of tmdnet_et_message_bwd2_ex
+struct Bwd2Ex {  // the strides / accumulation / source-pass extras of tmdnet_et_message_bwd2
   int ldggq, ldggk, ldggv, ldoq, ldok, ldov, ldopk, ldopv;
   const int32_t* tr;
   void* scratch;
@@ -1966,27 +1966,6 @@ extern "C" int tmdnet_et_message_bwd(int dtype, int n_nodes, int hidden, int hea
 
 extern "C" int tmdnet_et_message_bwd2(
     int dtype, int n_nodes, int hidden, int heads, const int32_t* row_ptr, const int32_t* src,
-    int max_pairs, const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v,
-    const void* vec_in, const void* pk, int ld_pk, const void* pv, int ld_pv, const void* cutoff,
-    const void* unit, const void* grad_x, const void* grad_vec, const void* gg_q, const void* gg_k,
-    const void* gg_v, const void* gg_vec, const void* gg_pk, int ld_ggpk, const void* gg_pv,
-    int ld_ggpv, const void* gg_cut, const void* gg_unit, void* d_grad_x, void* d_grad_vec,
-    void* d_q, void* d_k, void* d_v, void* d_vec, void* d_pk, void* d_pv, void* d_cut,
-    void* d_unit, int flags, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-#define TMD_BWD2(T)                                                                              \
-  return et::bwd2<T>(n_nodes, hidden, heads, row_ptr, src, max_pairs, q, ld_q, k, ld_k, v, ld_v, \
-                     vec_in, pk, ld_pk, pv, ld_pv, cutoff, unit, grad_x, grad_vec, gg_q, gg_k,   \
-                     gg_v, gg_vec, gg_pk, ld_ggpk, gg_pv, ld_ggpv, gg_cut, gg_unit, d_grad_x,    \
-                     d_grad_vec, d_q, d_k, d_v, d_vec, d_pk, d_pv, d_cut, d_unit, flags, st)
-  if (dtype == TMDNET_F32) TMD_BWD2(float);
-  if (dtype == TMDNET_F64) TMD_BWD2(double);
-#undef TMD_BWD2
-  return kUnsupported;
-}
-
-extern "C" int tmdnet_et_message_bwd2_ex(
-    int dtype, int n_nodes, int hidden, int heads, const int32_t* row_ptr, const int32_t* src,
     const int32_t* transpose, int max_pairs, const void* q, int ld_q, const void* k, int ld_k,
     const void* v, int ld_v, const void* vec_in, const void* pk, int ld_pk, const void* pv, int ld_pv,
     const void* cutoff, const void* unit, const void* grad_x, const void* grad_vec, const void* gg_q,
@@ -1998,11 +1977,14 @@ extern "C" int tmdnet_et_message_bwd2_ex(
   hipStream_t st = (hipStream_t)stream;
   const et::Bwd2Ex ex{ld_ggq, ld_ggk, ld_ggv, ld_dq, ld_dk, ld_dv, ld_dpk, ld_dpv, transpose, edge_scratch, pk_rows,
                       gg_pkv_scale};
+  // no stride, no source-pass scratch, no pair rows: the dense form, which makes no use of the record
+  const bool dense = !(ld_ggq | ld_ggk | ld_ggv | ld_dq | ld_dk | ld_dv | ld_dpk | ld_dpv) && !transpose &&
+                     !edge_scratch && !pk_rows && !gg_pkv_scale;
 #define TMD_BWD2(T)                                                                              \
   return et::bwd2<T>(n_nodes, hidden, heads, row_ptr, src, max_pairs, q, ld_q, k, ld_k, v, ld_v, \
                      vec_in, pk, ld_pk, pv, ld_pv, cutoff, unit, grad_x, grad_vec, gg_q, gg_k,   \
                      gg_v, gg_vec, gg_pk, ld_ggpk, gg_pv, ld_ggpv, gg_cut, gg_unit, d_grad_x,    \
-                     d_grad_vec, d_q, d_k, d_v, d_vec, d_pk, d_pv, d_cut, d_unit, flags, st, &ex)
+                     d_grad_vec, d_q, d_k, d_v, d_vec, d_pk, d_pv, d_cut, d_unit, flags, st, dense ? nullptr : &ex)
   if (dtype == TMDNET_F32) TMD_BWD2(float);
   if (dtype == TMDNET_F64) TMD_BWD2(double);
 #undef TMD_BWD2

@@ -110,20 +110,9 @@ extern "C" int tmdnet_et_epilogue_fwd(int dtype, int n_nodes, int hidden, const 
   return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
 }
 
-extern "C" int tmdnet_et_epilogue_bwd_acc(int dtype, int n_nodes, int hidden, const void* grad_x,
-                                          const void* grad_vec, const void* vecp, const void* o,
-                                          void* grad_vecp, void* grad_o, int accumulate, void* stream);
-
 extern "C" int tmdnet_et_epilogue_bwd(int dtype, int n_nodes, int hidden, const void* grad_x,
                                       const void* grad_vec, const void* vecp, const void* o,
-                                      void* grad_vecp, void* grad_o, void* stream) {
-  return tmdnet_et_epilogue_bwd_acc(dtype, n_nodes, hidden, grad_x, grad_vec, vecp, o, grad_vecp, grad_o, 0,
-                                    stream);
-}
-
-extern "C" int tmdnet_et_epilogue_bwd_acc(int dtype, int n_nodes, int hidden, const void* grad_x,
-                                          const void* grad_vec, const void* vecp, const void* o,
-                                          void* grad_vecp, void* grad_o, int accumulate, void* stream) {
+                                      void* grad_vecp, void* grad_o, int accumulate, void* stream) {
   const long long work = (long long)n_nodes * hidden;
   if (work <= 0) return kOk;
   const int tb = 256;
@@ -490,26 +479,11 @@ extern "C" int tmdnet_et_epilogue_ln_fwd(int dtype, int n_nodes, int hidden, con
   return kUnsupported;
 }
 
-extern "C" int tmdnet_ln_bwd_epilogue_w(int dtype, int n_nodes, int hidden, const void* grad_xn, const void* x,
-                                        const void* mean, const void* rstd, const void* ln_w,
-                                        const void* grad_res, const void* grad_res2, void* grad_x,
-                                        const void* grad_vec, const void* vecp, const void* o, void* grad_vecp,
-                                        void* grad_o, void* w_rows, int accumulate, void* stream);
-
 extern "C" int tmdnet_ln_bwd_epilogue(int dtype, int n_nodes, int hidden, const void* grad_xn, const void* x,
                                       const void* mean, const void* rstd, const void* ln_w,
-                                      const void* grad_res, void* grad_x, const void* grad_vec,
-                                      const void* vecp, const void* o, void* grad_vecp, void* grad_o,
-                                      void* stream) {
-  return tmdnet_ln_bwd_epilogue_w(dtype, n_nodes, hidden, grad_xn, x, mean, rstd, ln_w, grad_res, nullptr,
-                                  grad_x, grad_vec, vecp, o, grad_vecp, grad_o, nullptr, 0, stream);
-}
-
-extern "C" int tmdnet_ln_bwd_epilogue_w(int dtype, int n_nodes, int hidden, const void* grad_xn, const void* x,
-                                        const void* mean, const void* rstd, const void* ln_w,
-                                        const void* grad_res, const void* grad_res2, void* grad_x,
-                                        const void* grad_vec, const void* vecp, const void* o, void* grad_vecp,
-                                        void* grad_o, void* w_rows, int accumulate, void* stream) {
+                                      const void* grad_res, const void* grad_res2, void* grad_x,
+                                      const void* grad_vec, const void* vecp, const void* o, void* grad_vecp,
+                                      void* grad_o, void* w_rows, int accumulate, void* stream) {
   if (n_nodes < 0 || hidden <= 0 || !grad_xn || !x || !mean || !rstd || !ln_w || !grad_x) return kBadArgument;
   if (o && (!grad_o || (vecp && (!grad_vec || !grad_vecp)))) return kBadArgument;
   if (n_nodes == 0) return kOk;
@@ -529,13 +503,13 @@ extern "C" int tmdnet_ln_bwd_epilogue_w(int dtype, int n_nodes, int hidden, cons
   return kUnsupported;
 }
 
-extern "C" int tmdnet_et_adjoint_epi_ln2(int dtype, int n_nodes, int hidden, const void* gb_o, const void* gb_vecp,
-                                         const void* grad_x, const void* grad_vec, const void* vecp, const void* o,
-                                         const void* gbar_x_in, const void* gbar_vec_in, const void* gbar_vec_in2,
-                                         void* gbar_x_out, void* gbar_vec_out, void* vecp_bar, void* o_bar,
-                                         const void* x, const void* mean, const void* rstd, const void* ln_w,
-                                         const void* grad_xn, void* gbar_grad_xn, void* x_bar, void* w_bar_rows,
-                                         void* stream) {
+extern "C" int tmdnet_et_adjoint_epi_ln(int dtype, int n_nodes, int hidden, const void* gb_o, const void* gb_vecp,
+                                        const void* grad_x, const void* grad_vec, const void* vecp, const void* o,
+                                        const void* gbar_x_in, const void* gbar_vec_in, const void* gbar_vec_in2,
+                                        void* gbar_x_out, void* gbar_vec_out, void* vecp_bar, void* o_bar,
+                                        const void* x, const void* mean, const void* rstd, const void* ln_w,
+                                        const void* grad_xn, void* gbar_grad_xn, void* x_bar, void* w_bar_rows,
+                                        void* stream) {
   if (n_nodes < 0 || hidden <= 0 || !gbar_x_in) return kBadArgument;
   if (o && (!gb_o || !gbar_x_out || !o_bar || (vecp && (!gb_vecp || !grad_x || !grad_vec || !gbar_vec_out ||
                                                         !vecp_bar))))
@@ -555,15 +529,4 @@ extern "C" int tmdnet_et_adjoint_epi_ln2(int dtype, int n_nodes, int hidden, con
   if (dtype == TMDNET_F64) TMD_ADJ(double);
 #undef TMD_ADJ
   return kUnsupported;
-}
-
-extern "C" int tmdnet_et_adjoint_epi_ln(int dtype, int n_nodes, int hidden, const void* gb_o, const void* gb_vecp,
-                                        const void* grad_x, const void* grad_vec, const void* vecp, const void* o,
-                                        const void* gbar_x_in, const void* gbar_vec_in, void* gbar_x_out,
-                                        void* gbar_vec_out, void* vecp_bar, void* o_bar, const void* x,
-                                        const void* mean, const void* rstd, const void* ln_w, const void* grad_xn,
-                                        void* gbar_grad_xn, void* x_bar, void* w_bar_rows, void* stream) {
-  return tmdnet_et_adjoint_epi_ln2(dtype, n_nodes, hidden, gb_o, gb_vecp, grad_x, grad_vec, vecp, o, gbar_x_in,
-                                   gbar_vec_in, nullptr, gbar_x_out, gbar_vec_out, vecp_bar, o_bar, x, mean, rstd,
-                                   ln_w, grad_xn, gbar_grad_xn, x_bar, w_bar_rows, stream);
 }

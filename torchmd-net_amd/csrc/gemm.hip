@@ -1006,7 +1006,7 @@ struct XArgs {
   const unsigned short* Bp;
   const float* bias;
   float* C;
-  // epilogue extensions (tmdnet_gemm_x3_ex_f32, k_gemm's tmdnet_gemm_ex_f32 semantics): v = acc + bias (+ C)
+  // epilogue extensions (tmdnet_gemm_x3_f32, k_gemm's tmdnet_gemm_ex_f32 semantics): v = acc + bias (+ C)
   // -> pre[r][c] = v -> v = silu(v) (act) -> v *= rscale[r] -> v *= silu'(dpre[r][c]) -> C
   int act, ldx;
   float* pre;
@@ -1552,17 +1552,11 @@ extern "C" int tmdnet_proj_split_f32(int N, int K, const void* W, int ldw, void*
 
 // C [M][N] = A [M][K] W [N][K]^T (+ bias [N]) from Wp = tmdnet_proj_split_f32(W) (rows of the pieces
 // piece_stride elements apart: a row slice of a larger split is Wp + row0 * K with the full stride).
-// fp32 in / out on the bf16 MFMA.  K = 32 or 64, N % 16 == 0, 16-byte aligned rows.
-extern "C" int tmdnet_proj_f32(int M, int N, int K, const void* A, int lda, const void* Wp,
-                               long long piece_stride, const void* bias, void* C, int ldc, void* stream) {
-  return tmdnet_proj_rows_f32(M, N, K, A, lda, Wp, piece_stride, bias, C, ldc, nullptr, stream);
-}
-
-// tmdnet_proj_f32 stopping at a device row count: rows at or past min(M, max(0, *rows)) are not written
-// (rows NULL: every row).  The rows below it are the bits of the uncounted launch.
-extern "C" int tmdnet_proj_rows_f32(int M, int N, int K, const void* A, int lda, const void* Wp,
-                                    long long piece_stride, const void* bias, void* C, int ldc, const int32_t* rows,
-                                    void* stream) {
+// fp32 in / out on the bf16 MFMA.  K = 32 or 64, N % 16 == 0, 16-byte aligned rows.  rows (a device row
+// count, nullable): rows at or past min(M, max(0, *rows)) are not written (NULL: every row); the rows below it
+// are the bits of the uncounted launch.
+extern "C" int tmdnet_proj_f32(int M, int N, int K, const void* A, int lda, const void* Wp, long long piece_stride,
+                               const void* bias, void* C, int ldc, const int32_t* rows, void* stream) {
   if (M < 0 || N <= 0 || K <= 0 || !A || !Wp || !C) return kBadArgument;
   if (M == 0) return kOk;
   if ((K != 32 && K != 64) || N % 16 || lda < K || ldc < N || lda % 4 || ldc % 4 || piece_stride < (long long)N * K)
@@ -1589,18 +1583,11 @@ extern "C" int tmdnet_proj_rows_f32(int M, int N, int K, const void* A, int lda,
 }
 
 // S [M][N] = act(A W^T + bias) and (dA, D given) D = act'(A W^T + bias) * (dA W^T): tmdnet_proj_f32's
-// envelope and tiles with the ET dk / dv activation in the epilogue (k_proj_act_x3).
+// envelope and tiles with the ET dk / dv activation in the epilogue (k_proj_act_x3), and its device row count:
+// rows of S and D at or past min(M, max(0, *rows)) are not written (rows NULL: every row).
 extern "C" int tmdnet_proj_act_f32(int M, int N, int K, const void* A, const void* dA, int lda, const void* Wp,
                                    long long piece_stride, const void* bias, int act, void* S, void* D, int ldc,
-                                   void* stream) {
-  return tmdnet_proj_act_rows_f32(M, N, K, A, dA, lda, Wp, piece_stride, bias, act, S, D, ldc, nullptr, stream);
-}
-
-// tmdnet_proj_act_f32 stopping at a device row count (as tmdnet_proj_rows_f32): rows of S and D at or past
-// min(M, max(0, *rows)) are not written.
-extern "C" int tmdnet_proj_act_rows_f32(int M, int N, int K, const void* A, const void* dA, int lda, const void* Wp,
-                                        long long piece_stride, const void* bias, int act, void* S, void* D,
-                                        int ldc, const int32_t* rows, void* stream) {
+                                   const int32_t* rows, void* stream) {
   if (M < 0 || N <= 0 || K <= 0 || !A || !Wp || !S || act < kActSilu || act > kActSigmoid) return kBadArgument;
   if (D && !dA) return kBadArgument;
   if (M == 0) return kOk;
@@ -1643,18 +1630,13 @@ extern "C" int tmdnet_split_t_f32(int N, int K, const void* B, int ldb, void* Bp
 
 // C [M][N] = beta C + A [M][K] Bp^T + bias (Bp: tmdnet_proj_split_f32 of a [N][K] weight, or
 // tmdnet_split_t_f32 of a [K][N] right operand); fp32 in / out at fp32 accuracy on the bf16 MFMA.
-// K % 32 == 0, N % 16 == 0, 16-byte aligned rows and pointers.
+// K % 32 == 0, N % 16 == 0, 16-byte aligned rows and pointers.  tmdnet_gemm_ex_f32's epilogue, each part
+// optional (0 / NULL): pre (the pre-activation, row stride ldx), act (SiLU), rscale (per-row scale), dpre
+// (times silu'(dpre), row stride ldx) -- the Linear + SiLU stacks of large systems (TensorNet's edge MLP over
+// ~1M pair rows at C5) without separate activation passes.
 extern "C" int tmdnet_gemm_x3_f32(int M, int N, int K, const void* A, int lda, const void* Bp, const void* bias,
-                                  void* C, int ldc, int beta, void* stream) {
-  return tmdnet_gemm_x3_ex_f32(M, N, K, A, lda, Bp, bias, C, ldc, beta, 0, nullptr, nullptr, nullptr, 0, stream);
-}
-
-// tmdnet_gemm_x3_f32 with tmdnet_gemm_ex_f32's epilogue: pre (the pre-activation, row stride ldx), act (SiLU),
-// rscale (per-row scale), dpre (times silu'(dpre), row stride ldx) -- the Linear + SiLU stacks of large
-// systems (TensorNet's edge MLP over ~1M pair rows at C5) without separate activation passes.
-extern "C" int tmdnet_gemm_x3_ex_f32(int M, int N, int K, const void* A, int lda, const void* Bp, const void* bias,
-                                     void* C, int ldc, int beta, int act, void* pre, const void* rscale,
-                                     const void* dpre, int ldx, void* stream) {
+                                  void* C, int ldc, int beta, int act, void* pre, const void* rscale,
+                                  const void* dpre, int ldx, void* stream) {
   if (M < 0 || N <= 0 || K <= 0 || !A || !Bp || !C) return kBadArgument;
   if (M == 0) return kOk;
   if (K % 32 || N % 16 || lda < K || ldc < N || lda % 4 || ldc % 4) return kUnsupported;

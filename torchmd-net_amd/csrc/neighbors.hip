@@ -775,13 +775,16 @@ extern "C" size_t tmdnet_nl_workspace_bytes(int n_atoms, int strategy, const dou
   return nl::layout(n_atoms, strategy, box9 ? box9 : unit, cutoff_upper).total;
 }
 
-static int nl_build_any(int dtype, int strategy, const void* pos, const int64_t* batch, int n_atoms,
-                        const double* box9, int use_periodic, double cutoff_lower, double cutoff_upper,
-                        int max_pairs, int loop, int include_transpose, int32_t* neighbors, void* deltas,
-                        void* distances, int32_t* num_pairs, int32_t* row_ptr, int32_t* transpose_map,
-                        int pad_output, void* workspace, size_t workspace_bytes, int32_t* pair_row,
-                        int32_t* pair_edge, int n_pair_slots, int32_t* num_pair_rows, void* stream) {
+extern "C" int tmdnet_nl_build(int dtype, int strategy, const void* pos, const int64_t* batch, int n_atoms,
+                               const double* box9, int use_periodic, double cutoff_lower, double cutoff_upper,
+                               int max_pairs, int loop, int include_transpose, int32_t* neighbors, void* deltas,
+                               void* distances, int32_t* num_pairs, int32_t* row_ptr, int32_t* transpose_map,
+                               int pad_output, void* workspace, size_t workspace_bytes, int32_t* pair_row,
+                               int32_t* pair_edge, int n_pair_slots, int32_t* num_pair_rows, void* stream) {
   if (strategy != TMDNET_NL_BRUTE && strategy != TMDNET_NL_SHARED && strategy != TMDNET_NL_CELL)
+    return kBadArgument;
+  // no pairing: no pair operand at all; pairing: both maps and their capacity (nl::build checks the rest)
+  if (pair_row ? (!pair_edge || n_pair_slots <= 0) : (pair_edge || num_pair_rows || n_pair_slots != 0))
     return kBadArgument;
   double unit[9] = {0};
   const double* box = box9 ? box9 : unit;
@@ -799,50 +802,10 @@ static int nl_build_any(int dtype, int strategy, const void* pos, const int64_t*
   return kUnsupported;
 }
 
-extern "C" int tmdnet_nl_build(int dtype, int strategy, const void* pos, const int64_t* batch,
-                               int n_atoms, const double* box9, int use_periodic,
-                               double cutoff_lower, double cutoff_upper, int max_pairs, int loop,
-                               int include_transpose, int32_t* neighbors, void* deltas,
-                               void* distances, int32_t* num_pairs, int32_t* row_ptr,
-                               int32_t* transpose_map, int pad_output, void* workspace,
-                               size_t workspace_bytes, void* stream) {
-  return nl_build_any(dtype, strategy, pos, batch, n_atoms, box9, use_periodic, cutoff_lower, cutoff_upper,
-                      max_pairs, loop, include_transpose, neighbors, deltas, distances, num_pairs, row_ptr,
-                      transpose_map, pad_output, workspace, workspace_bytes, nullptr, nullptr, 0, nullptr, stream);
-}
-
-extern "C" int tmdnet_nl_build_paired(int dtype, int strategy, const void* pos, const int64_t* batch,
-                                      int n_atoms, const double* box9, int use_periodic, double cutoff_lower,
-                                      double cutoff_upper, int max_pairs, int loop, int include_transpose,
-                                      int32_t* neighbors, void* deltas, void* distances, int32_t* num_pairs,
-                                      int32_t* row_ptr, int32_t* transpose_map, int pad_output,
-                                      void* workspace, size_t workspace_bytes, int32_t* pair_row,
-                                      int32_t* pair_edge, int n_pair_slots, void* stream) {
-  return tmdnet_nl_build_paired_rows(dtype, strategy, pos, batch, n_atoms, box9, use_periodic, cutoff_lower,
-                                     cutoff_upper, max_pairs, loop, include_transpose, neighbors, deltas, distances,
-                                     num_pairs, row_ptr, transpose_map, pad_output, workspace, workspace_bytes,
-                                     pair_row, pair_edge, n_pair_slots, nullptr, stream);
-}
-
-extern "C" int tmdnet_nl_build_paired_rows(int dtype, int strategy, const void* pos, const int64_t* batch,
-                                           int n_atoms, const double* box9, int use_periodic, double cutoff_lower,
-                                           double cutoff_upper, int max_pairs, int loop, int include_transpose,
-                                           int32_t* neighbors, void* deltas, void* distances, int32_t* num_pairs,
-                                           int32_t* row_ptr, int32_t* transpose_map, int pad_output,
-                                           void* workspace, size_t workspace_bytes, int32_t* pair_row,
-                                           int32_t* pair_edge, int n_pair_slots, int32_t* num_pair_rows,
-                                           void* stream) {
-  if (!pair_row || !pair_edge || n_pair_slots <= 0) return kBadArgument;
-  return nl_build_any(dtype, strategy, pos, batch, n_atoms, box9, use_periodic, cutoff_lower, cutoff_upper,
-                      max_pairs, loop, include_transpose, neighbors, deltas, distances, num_pairs, row_ptr,
-                      transpose_map, pad_output, workspace, workspace_bytes, pair_row, pair_edge, n_pair_slots,
-                      num_pair_rows, stream);
-}
-
-extern "C" int tmdnet_nl_backward_multi(int dtype, int n_atoms, const int32_t* row_ptr,
-                                        const int32_t* transpose_map, int max_pairs, const void* grad_deltas,
-                                        const void* grad_distances, const void* grad_distances2, const void* deltas,
-                                        const void* distances, void* grad_pos, void* stream) {
+extern "C" int tmdnet_nl_backward(int dtype, int n_atoms, const int32_t* row_ptr, const int32_t* transpose_map,
+                                  int max_pairs, const void* grad_deltas, const void* grad_distances,
+                                  const void* grad_distances2, const void* deltas, const void* distances,
+                                  void* grad_pos, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int tb = 256;
   dim3 g((unsigned)(((size_t)n_atoms * nl::kNlLanes + tb - 1) / tb));
@@ -898,15 +861,6 @@ extern "C" int tmdnet_nl_backward_virial(int dtype, int n_atoms, const int32_t* 
                                       grad_distances2, deltas, distances, grad_pos, batch, n_mol, virial,
                                       atom_scratch, st);
   return kUnsupported;
-}
-
-extern "C" int tmdnet_nl_backward(int dtype, int n_atoms, const int32_t* row_ptr,
-                                  const int32_t* transpose_map, int max_pairs,
-                                  const void* grad_deltas, const void* grad_distances,
-                                  const void* deltas, const void* distances, void* grad_pos,
-                                  void* stream) {
-  return tmdnet_nl_backward_multi(dtype, n_atoms, row_ptr, transpose_map, max_pairs, grad_deltas, grad_distances,
-                                  nullptr, deltas, distances, grad_pos, stream);
 }
 
 extern "C" int tmdnet_nl_backward2(int dtype, int n_atoms, const int32_t* row_ptr, const int32_t* src,

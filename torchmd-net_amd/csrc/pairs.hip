@@ -177,16 +177,7 @@ extern "C" size_t tmdnet_pair_index_workspace_bytes(int n_nodes) {
 extern "C" int tmdnet_pair_index(int n_nodes, const int32_t* row_ptr, const int32_t* src, const int32_t* dst,
                                  const int32_t* transpose, int max_pairs, const int32_t* num_pairs,
                                  int sorted_rows, int32_t* pair_row, int32_t* pair_edge, int n_pair_slots,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
-  return tmdnet_pair_index_rows(n_nodes, row_ptr, src, dst, transpose, max_pairs, num_pairs, sorted_rows, pair_row,
-                                pair_edge, n_pair_slots, nullptr, workspace, workspace_bytes, stream);
-}
-
-extern "C" int tmdnet_pair_index_rows(int n_nodes, const int32_t* row_ptr, const int32_t* src, const int32_t* dst,
-                                      const int32_t* transpose, int max_pairs, const int32_t* num_pairs,
-                                      int sorted_rows, int32_t* pair_row, int32_t* pair_edge, int n_pair_slots,
-                                      int32_t* num_pair_rows, void* workspace, size_t workspace_bytes,
-                                      void* stream) {
+                                 int32_t* num_pair_rows, void* workspace, size_t workspace_bytes, void* stream) {
   if (n_nodes <= 0 || max_pairs < 0 || n_pair_slots < 0 || !row_ptr || !src || !transpose || !pair_row ||
       !pair_edge || (sorted_rows && !dst))
     return kBadArgument;

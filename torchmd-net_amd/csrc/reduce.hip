@@ -164,25 +164,6 @@ extern "C" int tmdnet_atom_sum_bwd(int dtype, int n_atoms, int n_mol, const void
   return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
 }
 
-extern "C" int tmdnet_dot_sum_fwd(int dtype, int n_atoms, int K, const void* h, int ld_h, const void* w,
-                                  const void* b0, int n_mol, const int64_t* batch, const void* std_,
-                                  const void* mean, void* y, void* stream) {
-  if (n_atoms < 0 || K <= 0 || ld_h < K || n_mol <= 0 || n_mol > red::kMaxBins || !h || !w || !batch || !y)
-    return kBadArgument;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == TMDNET_F32)
-    hipLaunchKernelGGL(red::k_dot_sum<float>, dim3(1), dim3(1024), 0, st, n_atoms, K, (const float*)h, ld_h,
-                       (const float*)w, (const float*)b0, n_mol, batch, (const float*)std_, (const float*)mean,
-                       (float*)y);
-  else if (dtype == TMDNET_F64)
-    hipLaunchKernelGGL(red::k_dot_sum<double>, dim3(1), dim3(1024), 0, st, n_atoms, K, (const double*)h, ld_h,
-                       (const double*)w, (const double*)b0, n_mol, batch, (const double*)std_,
-                       (const double*)mean, (double*)y);
-  else
-    return kUnsupported;
-  return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
-}
-
 extern "C" int tmdnet_dot_sum_bwd(int dtype, int n_atoms, int K, const void* grad_y, const int64_t* batch, int n_mol,
                                   const void* std_, const void* w, void* grad_h, void* stream) {
   if (n_atoms < 0 || K <= 0 || n_mol <= 0 || !grad_y || !batch || !w || !grad_h) return kBadArgument;
@@ -201,22 +182,27 @@ extern "C" int tmdnet_dot_sum_bwd(int dtype, int n_atoms, int K, const void* gra
   return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
 }
 
-// tmdnet_dot_sum_fwd for large systems: the row products over the whole grid into atom_buf [n_atoms] (the
-// per-atom energies before std / mean), then the per-molecule sums.  atom_buf NULL: tmdnet_dot_sum_fwd.
-extern "C" int tmdnet_dot_sum_fwd_atoms(int dtype, int n_atoms, int K, const void* h, int ld_h, const void* w,
-                                        const void* b0, int n_mol, const int64_t* batch, const void* std_,
-                                        const void* mean, void* atom_buf, void* y, void* stream) {
-  if (!atom_buf) return tmdnet_dot_sum_fwd(dtype, n_atoms, K, h, ld_h, w, b0, n_mol, batch, std_, mean, y, stream);
+// atom_buf NULL: one workgroup forms the row products and the per-molecule sums.  atom_buf [n_atoms] (large
+// systems): the row products over the whole grid into it (the per-atom energies before std / mean), then the
+// per-molecule sums.
+extern "C" int tmdnet_dot_sum_fwd(int dtype, int n_atoms, int K, const void* h, int ld_h, const void* w,
+                                  const void* b0, int n_mol, const int64_t* batch, const void* std_,
+                                  const void* mean, void* atom_buf, void* y, void* stream) {
   if (n_atoms < 0 || K <= 0 || ld_h < K || n_mol <= 0 || n_mol > red::kMaxBins || !h || !w || !batch || !y)
     return kBadArgument;
   hipStream_t st = (hipStream_t)stream;
   const dim3 g((unsigned)(((long long)n_atoms * 16 + 255) / 256));
-#define TMD_DOTS(T)                                                                                            \
-  if (n_atoms > 0)                                                                                             \
-    hipLaunchKernelGGL(red::k_row_dot<T>, g, dim3(256), 0, st, n_atoms, K, (const T*)h, ld_h, (const T*)w,     \
-                       (const T*)b0, (T*)atom_buf);                                                            \
-  hipLaunchKernelGGL(red::k_atom_runs<T>, dim3(1), dim3(1024), 0, st, n_atoms, n_mol, (const T*)atom_buf, batch, \
-                     (const T*)std_, (const T*)mean, (T*)y);
+#define TMD_DOTS(T)                                                                                               \
+  if (!atom_buf) {                                                                                                \
+    hipLaunchKernelGGL(red::k_dot_sum<T>, dim3(1), dim3(1024), 0, st, n_atoms, K, (const T*)h, ld_h, (const T*)w, \
+                       (const T*)b0, n_mol, batch, (const T*)std_, (const T*)mean, (T*)y);                        \
+  } else {                                                                                                        \
+    if (n_atoms > 0)                                                                                              \
+      hipLaunchKernelGGL(red::k_row_dot<T>, g, dim3(256), 0, st, n_atoms, K, (const T*)h, ld_h, (const T*)w,      \
+                         (const T*)b0, (T*)atom_buf);                                                             \
+    hipLaunchKernelGGL(red::k_atom_runs<T>, dim3(1), dim3(1024), 0, st, n_atoms, n_mol, (const T*)atom_buf,       \
+                       batch, (const T*)std_, (const T*)mean, (T*)y);                                             \
+  }
   if (dtype == TMDNET_F32) {
     TMD_DOTS(float)
   } else if (dtype == TMDNET_F64) {

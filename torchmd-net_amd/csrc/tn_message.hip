@@ -738,12 +738,12 @@ extern "C" int tmdnet_tn_message_fwd(int dtype, int n_nodes, int hidden, const i
   })
 }
 
-extern "C" int tmdnet_tn_message_bwd_add(int dtype, int n_nodes, int hidden, const int32_t* row_ptr,
-                                         const int32_t* src, int max_pairs, double self0_mult,
-                                         const int32_t* pad_pairs, int pad_capacity,
-                                         const void* edge_attr, int ld_ea, const void* comp,
-                                         const void* grad_msg, const void* g_comp_add, void* g_edge_attr,
-                                         void* g_comp, void* stream) {
+extern "C" int tmdnet_tn_message_bwd(int dtype, int n_nodes, int hidden, const int32_t* row_ptr,
+                                     const int32_t* src, int max_pairs, double self0_mult,
+                                     const int32_t* pad_pairs, int pad_capacity,
+                                     const void* edge_attr, int ld_ea, const void* comp,
+                                     const void* grad_msg, const void* g_comp_add, void* g_edge_attr,
+                                     void* g_comp, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   TN_DISPATCH(dtype, {
     auto a = tn::base<T>(n_nodes, hidden, row_ptr, src, max_pairs, self0_mult, pad_pairs,
@@ -756,17 +756,6 @@ extern "C" int tmdnet_tn_message_bwd_add(int dtype, int n_nodes, int hidden, con
     if (rc) return rc;
     return tn::launch_msg_bwd_src<T>(a, st);
   })
-}
-
-extern "C" int tmdnet_tn_message_bwd(int dtype, int n_nodes, int hidden, const int32_t* row_ptr,
-                                     const int32_t* src, int max_pairs, double self0_mult,
-                                     const int32_t* pad_pairs, int pad_capacity,
-                                     const void* edge_attr, int ld_ea, const void* comp,
-                                     const void* grad_msg, void* g_edge_attr, void* g_comp,
-                                     void* stream) {
-  return tmdnet_tn_message_bwd_add(dtype, n_nodes, hidden, row_ptr, src, max_pairs, self0_mult, pad_pairs,
-                                   pad_capacity, edge_attr, ld_ea, comp, grad_msg, nullptr, g_edge_attr, g_comp,
-                                   stream);
 }
 
 // Pair-row forms of the message (large systems): edge_attr / g_edge_attr hold one row per pair slot of

@@ -172,7 +172,8 @@ Built nl_build(const std::string& strategy_in, const Tensor& pos, const Tensor& 
   check(tmdnet_nl_build(dcode(pos), st, pos.data_ptr(), batch.data_ptr<int64_t>(), n, bp, use_periodic ? 1 : 0, cl,
                         cu, cap, loop ? 1 : 0, include_transpose ? 1 : 0, ptr<int32_t>(B.nb), ptr(B.dl),
                         ptr(B.dist), ptr<int32_t>(B.num), ptr<int32_t>(B.row_ptr), ptr<int32_t>(B.tr),
-                        pad ? 1 : 0, ws.data_ptr(), static_cast<size_t>(ws.numel()), stream_of(pos)),
+                        pad ? 1 : 0, ws.data_ptr(), static_cast<size_t>(ws.numel()), nullptr, nullptr, 0, nullptr,
+                        stream_of(pos)),
         "tmdnet_nl_build");
   return B;
 }
@@ -358,7 +359,7 @@ struct NlGeomBwd : public Function<NlGeomBwd> {
     Tensor gpos = at::empty_like(pos);
     Tensor gd_ = contig(gd), gr_ = contig(gr);
     check(tmdnet_nl_backward(dcode(pos), g.n(), ptr<int32_t>(row_ptr), ptr<int32_t>(tr), g.E(), ptr(gd_), ptr(gr_),
-                             ptr(dl), ptr(dist), ptr(gpos), stream_of(pos)),
+                             nullptr, ptr(dl), ptr(dist), ptr(gpos), stream_of(pos)),
           "tmdnet_nl_backward");
     keep_graph(ctx, g);
     ctx->save_for_backward({pos, gd_, gr_, dl, dist});
@@ -492,8 +493,8 @@ struct EdgeGeomBwd : public Function<EdgeGeomBwd> {
     Tensor g_r = at::empty_like(dist), g_dl = at::empty_like(dl);
     Tensor gf_ = contig(gf), gC_ = contig(gC), gu_ = contig(gu);
     check(tmdnet_edge_geom_bwd(dcode(dist), E, static_cast<int>(mu.size(0)), static_cast<int>(rbf), ptr<int32_t>(src),
-                               ptr<int32_t>(dst), ptr(dl), ptr(dist), ptr(mu), ptr(beta), cl, cu, ptr(gf_), ptr(gC_),
-                               ptr(gu_), ptr(g_r), ptr(g_dl), stream_of(dist)),
+                               ptr<int32_t>(dst), ptr(dl), ptr(dist), ptr(mu), ptr(beta), cl, cu, ptr(gf_), nullptr,
+                               nullptr, ptr(gC_), nullptr, nullptr, ptr(gu_), ptr(g_r), ptr(g_dl), stream_of(dist)),
           "tmdnet_edge_geom_bwd");
     keep_geo(ctx, cl, cu, rbf);
     ctx->save_for_backward({dl, dist, gf_, gC_, gu_, src, dst, mu, beta});
@@ -552,7 +553,7 @@ struct EdgeGeom : public Function<EdgeGeom> {
     Tensor u = at::empty({E, 3}, opts(dist));
     check(tmdnet_edge_geom_fwd(dcode(dist), E, R, static_cast<int>(rbf), ptr<int32_t>(src), ptr<int32_t>(dst),
                                ptr(dl), ptr(dist), ptr(mu), ptr(beta), cl, cu, want_rbf ? ptr(f) : nullptr,
-                               ptr(C), ptr(u), stream_of(dist)),
+                               ptr(C), ptr(u), nullptr, 0, nullptr, nullptr, stream_of(dist)),
           "tmdnet_edge_geom_fwd");
     keep_geo(ctx, cl, cu, rbf);
     ctx->saved_data["want_rbf"] = want_rbf;
@@ -708,12 +709,14 @@ struct EtMsgBwd : public Function<EtMsgBwd> {
     Tensor d_pk = pk.defined() ? at::empty({E, H}, o) : Tensor();
     Tensor d_pv = pv.defined() ? at::empty({E, 3 * H}, o) : Tensor();
     Tensor d_C = at::empty({E}, o), d_u = at::empty({E, 3}, o);
-    check(tmdnet_et_message_bwd2(dcode(q), N, H, heads, ptr<int32_t>(g.row_ptr), ptr<int32_t>(g.src), E, ptr(q), ld(q),
-                                 ptr(k), ld(k), ptr(v), ld(v), ptr(vec), ptr(pk), ld(pk), ptr(pv), ld(pv), ptr(C),
-                                 ptr(u), ptr(gx), ptr(gvec), ptr(ggq), ptr(ggk), ptr(ggv), ptr(ggw), ptr(ggpk),
-                                 ld(ggpk), ptr(ggpv), ld(ggpv), ptr(ggC), ptr(ggu), ptr(d_gx), ptr(d_gvec), ptr(d_q),
-                                 ptr(d_k), ptr(d_v), vec.defined() ? ptr(d_vec) : nullptr, ptr(d_pk), ptr(d_pv),
-                                 ptr(d_C), ptr(d_u), static_cast<int>(ctx->saved_data["acts"].toInt()), stream_of(q)),
+    // dense rows (strides 0), the atomic source pass (no transpose map / scratch), per-edge projection rows
+    check(tmdnet_et_message_bwd2(dcode(q), N, H, heads, ptr<int32_t>(g.row_ptr), ptr<int32_t>(g.src), nullptr, E, ptr(q),
+                                 ld(q), ptr(k), ld(k), ptr(v), ld(v), ptr(vec), ptr(pk), ld(pk), ptr(pv), ld(pv), ptr(C),
+                                 ptr(u), ptr(gx), ptr(gvec), ptr(ggq), 0, ptr(ggk), 0, ptr(ggv), 0, ptr(ggw), ptr(ggpk),
+                                 ld(ggpk), ptr(ggpv), ld(ggpv), ptr(ggC), ptr(ggu), ptr(d_gx), ptr(d_gvec), ptr(d_q), 0,
+                                 ptr(d_k), 0, ptr(d_v), 0, vec.defined() ? ptr(d_vec) : nullptr, ptr(d_pk), 0, ptr(d_pv),
+                                 0, ptr(d_C), ptr(d_u), nullptr, nullptr, nullptr,
+                                 static_cast<int>(ctx->saved_data["acts"].toInt()), stream_of(q)),
           "tmdnet_et_message_bwd2");
     return {d_gx, d_gvec, d_q, d_k, d_v, vec.defined() ? d_vec : Tensor(), d_pk, d_pv, d_C, d_u,
             Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
@@ -926,7 +929,7 @@ struct TnMessageBwd : public Function<TnMessageBwd> {
     Tensor gm = gmsg.contiguous();
     Tensor gea = at::empty({E, 3 * H}, opts(Tc)), gT = at::empty_like(Tc);
     check(tmdnet_tn_message_bwd(dcode(Tc), N, H, ptr<int32_t>(row_ptr), ptr<int32_t>(src), E, m, nullptr, 0, ptr(ea),
-                                ld(ea), ptr(Tc), ptr(gm), ptr(gea), ptr(gT), stream_of(Tc)),
+                                ld(ea), ptr(Tc), ptr(gm), nullptr, ptr(gea), ptr(gT), stream_of(Tc)),
           "tmdnet_tn_message_bwd");
     keep_graph(ctx, g);
     ctx->saved_data["m"] = m;
@@ -1176,7 +1179,7 @@ bool gemm_x3_into(const GemmP& p) {
   check(rc, "tmdnet_split");
   rc = tmdnet_gemm_x3_f32(p.M(), N, K, p.A.data_ptr(), static_cast<int>(p.A.stride(0)), bp.data_ptr(),
                           p.bias.defined() ? p.bias.data_ptr() : nullptr, p.C.data_ptr(),
-                          static_cast<int>(p.C.stride(0)), p.beta ? 1 : 0, st);
+                          static_cast<int>(p.C.stride(0)), p.beta ? 1 : 0, 0, nullptr, nullptr, nullptr, 0, st);
   if (rc != TMDNET_UNSUPPORTED) check(rc, "tmdnet_gemm_x3_f32");
   return rc != TMDNET_UNSUPPORTED;
 }
@@ -1207,7 +1210,7 @@ void proj_into(const Tensor& A, const Tensor& W, const Tensor& Wp, const Tensor&
   if (Wp.defined() && M > 0) {
     const int rc = tmdnet_proj_f32(M, N, K, A.data_ptr(), static_cast<int>(A.stride(0)), Wp.data_ptr(),
                                    static_cast<long long>(N) * K, bias.defined() ? bias.data_ptr() : nullptr,
-                                   out.data_ptr(), static_cast<int>(out.stride(0)), stream_of(A));
+                                   out.data_ptr(), static_cast<int>(out.stride(0)), nullptr, stream_of(A));
     if (rc != TMDNET_UNSUPPORTED) {
       check(rc, "tmdnet_proj_f32");
       return;
@@ -1408,20 +1411,20 @@ variable_list stack_backward_dr(const StackActs& A, Tensor gX, Tensor gV, const 
   } else if (c.out_norm) {  // back through out_norm and the last layer's epilogue in one kernel
     Tensor g = at::empty_like(gX);
     const Tensor& on_w = P[P.size() - 2];
-    check(tmdnet_ln_bwd_epilogue_w(dcode(gX), static_cast<int>(N), static_cast<int>(H), ptr(gX), ptr(A.x_pre),
-                                   ptr(A.mean_o), ptr(A.rstd_o), ptr(on_w), nullptr, nullptr, ptr(g), ptr(gV),
-                                   ptr(A.vecp[L - 1]), ptr(A.o[L - 1]), ptr(g_vecp[L - 1]), ptr(g_o[L - 1]), nullptr, 0,
-                                   stream_of(gX)),
-          "tmdnet_ln_bwd_epilogue_w");
+    check(tmdnet_ln_bwd_epilogue(dcode(gX), static_cast<int>(N), static_cast<int>(H), ptr(gX), ptr(A.x_pre),
+                                 ptr(A.mean_o), ptr(A.rstd_o), ptr(on_w), nullptr, nullptr, ptr(g), ptr(gV),
+                                 ptr(A.vecp[L - 1]), ptr(A.o[L - 1]), ptr(g_vecp[L - 1]), ptr(g_o[L - 1]), nullptr, 0,
+                                 stream_of(gX)),
+          "tmdnet_ln_bwd_epilogue");
     gX = g;
     epi_done = true;
   }
   for (int64_t l = L - 1; l >= 0; --l) {
     const Tensor* p = P.data() + l * np;
     if (!epi_done)
-      check(tmdnet_et_epilogue_bwd_acc(dcode(gX), static_cast<int>(N), static_cast<int>(H), ptr(gX), ptr(gV),
-                                       ptr(A.vecp[l]), ptr(A.o[l]), ptr(g_vecp[l]), ptr(g_o[l]), 0, stream_of(gX)),
-            "tmdnet_et_epilogue_bwd_acc");
+      check(tmdnet_et_epilogue_bwd(dcode(gX), static_cast<int>(N), static_cast<int>(H), ptr(gX), ptr(gV),
+                                   ptr(A.vecp[l]), ptr(A.o[l]), ptr(g_vecp[l]), ptr(g_o[l]), 0, stream_of(gX)),
+            "tmdnet_et_epilogue_bwd");
     Tensor g_xa = g_xa_pre;
     g_xa_pre = Tensor();
     if (!g_xa.defined()) {
@@ -1469,12 +1472,12 @@ variable_list stack_backward_dr(const StackActs& A, Tensor gX, Tensor gV, const 
                         P[(l - 1) * np + 9], g_vecp[l - 1], g_o[l - 1], &g_xa_pre);
     } else {
       g_x = at::empty_like(g_xn);
-      check(tmdnet_ln_bwd_epilogue_w(dcode(gX), static_cast<int>(N), static_cast<int>(H), ptr(g_xn), ptr(A.x[l]),
-                                     ptr(A.mean[l]), ptr(A.rstd[l]), ptr(p[0]), ptr(gX), nullptr, ptr(g_x),
-                                     ptr(g_vec_in), prev ? ptr(A.vecp[l - 1]) : nullptr,
-                                     prev ? ptr(A.o[l - 1]) : nullptr, prev ? ptr(g_vecp[l - 1]) : nullptr,
-                                     prev ? ptr(g_o[l - 1]) : nullptr, nullptr, 0, stream_of(gX)),
-            "tmdnet_ln_bwd_epilogue_w");
+      check(tmdnet_ln_bwd_epilogue(dcode(gX), static_cast<int>(N), static_cast<int>(H), ptr(g_xn), ptr(A.x[l]),
+                                   ptr(A.mean[l]), ptr(A.rstd[l]), ptr(p[0]), ptr(gX), nullptr, ptr(g_x),
+                                   ptr(g_vec_in), prev ? ptr(A.vecp[l - 1]) : nullptr,
+                                   prev ? ptr(A.o[l - 1]) : nullptr, prev ? ptr(g_vecp[l - 1]) : nullptr,
+                                   prev ? ptr(g_o[l - 1]) : nullptr, nullptr, 0, stream_of(gX)),
+            "tmdnet_ln_bwd_epilogue");
     }
     epi_done = prev;
     gX = g_x;
@@ -1932,11 +1935,11 @@ variable_list stack_backward_fused(const StackActs& A, const FusedAux& F, Tensor
                      P[(L - 1) * np + 9], g_vecp[L - 1], g_o[L - 1], &g_xa_pre);
   } else {  // back through out_norm and the last layer's epilogue in one kernel
     Tensor g = at::empty_like(gX);
-    check(tmdnet_ln_bwd_epilogue_w(TMDNET_F32, static_cast<int>(N), static_cast<int>(H), ptr(gX), ptr(A.x_pre),
-                                   ptr(A.mean_o), ptr(A.rstd_o), ptr(P[P.size() - 2]), nullptr, nullptr, ptr(g), ptr(gV),
-                                   ptr(A.vecp[L - 1]), ptr(A.o[L - 1]), ptr(g_vecp[L - 1]), ptr(g_o[L - 1]), nullptr, 0,
-                                   st),
-          "tmdnet_ln_bwd_epilogue_w");
+    check(tmdnet_ln_bwd_epilogue(TMDNET_F32, static_cast<int>(N), static_cast<int>(H), ptr(gX), ptr(A.x_pre),
+                                 ptr(A.mean_o), ptr(A.rstd_o), ptr(P[P.size() - 2]), nullptr, nullptr, ptr(g), ptr(gV),
+                                 ptr(A.vecp[L - 1]), ptr(A.o[L - 1]), ptr(g_vecp[L - 1]), ptr(g_o[L - 1]), nullptr, 0,
+                                 st),
+          "tmdnet_ln_bwd_epilogue");
     gX = g;
   }
   for (int64_t l = L - 1; l >= 0; --l) {
@@ -1974,12 +1977,12 @@ variable_list stack_backward_fused(const StackActs& A, const FusedAux& F, Tensor
                         P[(l - 1) * np + 9], g_vecp[l - 1], g_o[l - 1], &g_xa_pre);
     } else {
       g_x = at::empty_like(g_xn);
-      check(tmdnet_ln_bwd_epilogue_w(TMDNET_F32, static_cast<int>(N), static_cast<int>(H), ptr(g_xn), ptr(A.x[l]),
-                                     ptr(A.mean[l]), ptr(A.rstd[l]), ptr(p[0]), ptr(gX), nullptr, ptr(g_x), ptr(g_vec_in),
-                                     prev ? ptr(A.vecp[l - 1]) : nullptr, prev ? ptr(A.o[l - 1]) : nullptr,
-                                     prev ? ptr(g_vecp[l - 1]) : nullptr, prev ? ptr(g_o[l - 1]) : nullptr, nullptr, 0,
-                                     st),
-            "tmdnet_ln_bwd_epilogue_w");
+      check(tmdnet_ln_bwd_epilogue(TMDNET_F32, static_cast<int>(N), static_cast<int>(H), ptr(g_xn), ptr(A.x[l]),
+                                   ptr(A.mean[l]), ptr(A.rstd[l]), ptr(p[0]), ptr(gX), nullptr, ptr(g_x), ptr(g_vec_in),
+                                   prev ? ptr(A.vecp[l - 1]) : nullptr, prev ? ptr(A.o[l - 1]) : nullptr,
+                                   prev ? ptr(g_vecp[l - 1]) : nullptr, prev ? ptr(g_o[l - 1]) : nullptr, nullptr, 0,
+                                   st),
+            "tmdnet_ln_bwd_epilogue");
     }
     gX = g_x;
     gV = g_vec_in;
@@ -2068,14 +2071,14 @@ std::tuple<Tensor, Tensor> et_energy_forces(
     check(tmdnet_pair_index(static_cast<int>(N), ptr<int32_t>(row_ptr), ptr<int32_t>(src), ptr<int32_t>(dst),
                             ptr<int32_t>(tr), static_cast<int>(E), ptr<int32_t>(B.num), sorted_rows ? 1 : 0,
                             ptr<int32_t>(F.pair_row), ptr<int32_t>(F.pair_edge), static_cast<int>(F.pair_edge.size(0)),
-                            pws.data_ptr(), static_cast<size_t>(pws.numel()), st),
+                            nullptr, pws.data_ptr(), static_cast<size_t>(pws.numel()), st),
           "tmdnet_pair_index");
   }
   // edge geometry
   Tensor f = at::empty({E, R}, o), C = at::empty({E}, o), u = at::empty({E, 3}, o);
   check(tmdnet_edge_geom_fwd(dt, static_cast<int>(E), static_cast<int>(R), static_cast<int>(rbf_type),
                              ptr<int32_t>(src), ptr<int32_t>(dst), ptr(dl), ptr(dist), ptr(mu), ptr(beta), cl, cu,
-                             ptr(f), ptr(C), ptr(u), st),
+                             ptr(f), ptr(C), ptr(u), nullptr, 0, nullptr, nullptr, st),
         "tmdnet_edge_geom_fwd");
   // neighbour embedding: W = distance_proj(f); [x | x_nb] by the aggregation kernel; combine.  Large systems
   // (the fused stack's envelope): distance_proj formed inside the aggregation kernel from the pair rows'
@@ -2193,15 +2196,15 @@ std::tuple<Tensor, Tensor> et_energy_forces(
     gemm_group_into({{gW, val(nb_dist_w_), false, Tensor(), gf, false}});
   }
   Tensor g_r = at::empty({E}, o), g_dl = at::empty({E, 3}, o);
-  check(tmdnet_edge_geom_bwd_multi(dt, static_cast<int>(E), static_cast<int>(R), static_cast<int>(rbf_type),
-                                   ptr<int32_t>(src), ptr<int32_t>(dst), ptr(dl), ptr(dist), ptr(mu), ptr(beta), cl, cu,
-                                   ptr(gf), nullptr, nullptr, ptr(gs[2]), ptr(gC_nb), nullptr, ptr(gs[3]), ptr(g_r),
-                                   ptr(g_dl), st),
-        "tmdnet_edge_geom_bwd_multi");
+  check(tmdnet_edge_geom_bwd(dt, static_cast<int>(E), static_cast<int>(R), static_cast<int>(rbf_type),
+                             ptr<int32_t>(src), ptr<int32_t>(dst), ptr(dl), ptr(dist), ptr(mu), ptr(beta), cl, cu,
+                             ptr(gf), nullptr, nullptr, ptr(gs[2]), ptr(gC_nb), nullptr, ptr(gs[3]), ptr(g_r),
+                             ptr(g_dl), st),
+        "tmdnet_edge_geom_bwd");
   Tensor neg_dy = at::empty({N, 3}, o);
-  check(tmdnet_nl_backward_multi(dt, static_cast<int>(N), ptr<int32_t>(row_ptr), ptr<int32_t>(tr), static_cast<int>(E),
-                                 ptr(g_dl), ptr(g_r), ptr(gs[1]), ptr(dl), ptr(dist), ptr(neg_dy), st),
-        "tmdnet_nl_backward_multi");
+  check(tmdnet_nl_backward(dt, static_cast<int>(N), ptr<int32_t>(row_ptr), ptr<int32_t>(tr), static_cast<int>(E),
+                           ptr(g_dl), ptr(g_r), ptr(gs[1]), ptr(dl), ptr(dist), ptr(neg_dy), st),
+        "tmdnet_nl_backward");
   if (perm.defined()) {  // back to the caller's atom order
     Tensor out = at::empty_like(neg_dy);
     out.index_copy_(0, perm, neg_dy);

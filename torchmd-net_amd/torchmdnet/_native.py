@@ -39,20 +39,14 @@ SZ = ctypes.c_size_t
 # name -> (restype, argtypes); must match include/tmdnet.h exactly (tests check the exports)
 SIGNATURES = {
     "tmdnet_nl_workspace_bytes": (SZ, [I, I, P, D]),
-    "tmdnet_nl_build": (I, [I, I, P, P, I, P, I, D, D, I, I, I, P, P, P, P, P, P, I, P, SZ, P]),
-    "tmdnet_nl_build_paired": (I, [I, I, P, P, I, P, I, D, D, I, I, I, P, P, P, P, P, P, I, P, SZ, P, P, I, P]),
-    "tmdnet_nl_build_paired_rows": (I, [I, I, P, P, I, P, I, D, D, I, I, I, P, P, P, P, P, P, I, P, SZ, P, P, I, P,
+    "tmdnet_nl_build": (I, [I, I, P, P, I, P, I, D, D, I, I, I, P, P, P, P, P, P, I, P, SZ, P, P, I, P,
                                         P]),
-    "tmdnet_nl_backward": (I, [I, I, P, P, I, P, P, P, P, P, P]),
-    "tmdnet_nl_backward_multi": (I, [I, I, P, P, I, P, P, P, P, P, P, P]),
+    "tmdnet_nl_backward": (I, [I, I, P, P, I, P, P, P, P, P, P, P]),
     "tmdnet_nl_backward_virial": (I, [I, I, P, P, I, P, P, P, P, P, P, P, I, P, P, P]),
     "tmdnet_nl_backward2": (I, [I, I, P, P, P, I, P, P, P, P, P, P, P, P]),
     "tmdnet_nl_backward_edges": (I, [I, I, P, I, P, P, P, P, P, P]),
-    "tmdnet_edge_geom_fwd": (I, [I, I, I, I, P, P, P, P, P, P, D, D, P, P, P, P]),
-    "tmdnet_edge_geom_fwd_rows": (I, [I, I, I, I, P, P, P, P, P, P, D, D, P, P, P, P, I, P, P]),
-    "tmdnet_edge_geom_fwd_rows2": (I, [I, I, I, I, P, P, P, P, P, P, D, D, P, P, P, P, I, P, P, P]),
-    "tmdnet_edge_geom_bwd": (I, [I, I, I, I, P, P, P, P, P, P, D, D, P, P, P, P, P, P]),
-    "tmdnet_edge_geom_bwd_multi": (I, [I, I, I, I, P, P, P, P, P, P, D, D, P, P, P, P, P, P, P, P, P, P]),
+    "tmdnet_edge_geom_fwd": (I, [I, I, I, I, P, P, P, P, P, P, D, D, P, P, P, P, I, P, P, P]),
+    "tmdnet_edge_geom_bwd": (I, [I, I, I, I, P, P, P, P, P, P, D, D, P, P, P, P, P, P, P, P, P, P]),
     "tmdnet_edge_geom_bwd2": (I, [I, I, I, I, P, P, P, P, P, P, D, D, P, P, P, P, P, P, P, P, P, P, P]),
     "tmdnet_et_message_fwd": (I, [I, I, I, I, P, P, I, P, I, P, I, P, I, P, P, I, P, I, P, P, P, P, I, P, P,
                                   P]),
@@ -60,24 +54,18 @@ SIGNATURES = {
                                   P, P, P, P, P, P, P, P, P, P, P, I, P, P, P]),
     "tmdnet_rbf_deriv": (I, [I, I, I, P, P, P, D, D, P, I, P, P]),
     "tmdnet_pair_index_workspace_bytes": (SZ, [I]),
-    "tmdnet_pair_index": (I, [I, P, P, P, P, I, P, I, P, P, I, P, SZ, P]),
-    "tmdnet_pair_index_rows": (I, [I, P, P, P, P, I, P, I, P, P, I, P, P, SZ, P]),
-    "tmdnet_et_message_bwd2": (I, [I, I, I, I, P, P, I, P, I, P, I, P, I, P, P, I, P, I, P, P, P, P,
-                                   P, P, P, P, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, P, I, P]),
-    "tmdnet_et_message_bwd2_ex": (I, [I, I, I, I, P, P, P, I, P, I, P, I, P, I, P, P, I, P, I, P, P, P, P,
+    "tmdnet_pair_index": (I, [I, P, P, P, P, I, P, I, P, P, I, P, P, SZ, P]),
+    "tmdnet_et_message_bwd2": (I, [I, I, I, I, P, P, P, I, P, I, P, I, P, I, P, P, I, P, I, P, P, P, P,
                                       P, I, P, I, P, I, P, P, I, P, I, P, P,
                                       P, P, P, I, P, I, P, I, P, P, I, P, I, P, P, P, P, P, I, P]),
     "tmdnet_et_epilogue_fwd": (I, [I, I, I, P, P, P, P, P, P, P, P]),
-    "tmdnet_et_epilogue_bwd": (I, [I, I, I, P, P, P, P, P, P, P]),
-    "tmdnet_et_epilogue_bwd_acc": (I, [I, I, I, P, P, P, P, P, P, I, P]),
+    "tmdnet_et_epilogue_bwd": (I, [I, I, I, P, P, P, P, P, P, I, P]),
     "tmdnet_et_epilogue_ln_fwd": (I, [I, I, I, P, P, P, P, P, P, P, D, P, P, P, P, P, P]),
-    "tmdnet_ln_bwd_epilogue": (I, [I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "tmdnet_ln_bwd_epilogue_w": (I, [I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P]),
+    "tmdnet_ln_bwd_epilogue": (I, [I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P]),
     "tmdnet_et_oproj_epilogue_f32": (I, [I, I] + [P] * 11),
     "tmdnet_et_ln_mix_f32": (I, [I, I, P, P, P, D, P, P, I, P, P, P, P, P, P, I, P, P]),
     "tmdnet_et_lnbwd_oproj_f32": (I, [I, I] + [P] * 15),
-    "tmdnet_et_adjoint_epi_ln": (I, [I, I, I] + [P] * 21),
-    "tmdnet_et_adjoint_epi_ln2": (I, [I, I, I] + [P] * 22),
+    "tmdnet_et_adjoint_epi_ln": (I, [I, I, I] + [P] * 22),
     "tmdnet_eq_head_fwd": (I, [I, I, I, P, P, P, P, P, P, P]),
     "tmdnet_eq_head_bwd": (I, [I, I, I, P, P, P, P, P, P]),
     "tmdnet_eq_head_bwd_weights": (I, [I, I, I, P, P, P, P, P, P, P, P]),
@@ -97,8 +85,7 @@ SIGNATURES = {
     "tmdnet_tn_embed_bwd2": (I, [I, I, I, P, P, I, D, P, I, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
                                  P]),
     "tmdnet_tn_message_fwd": (I, [I, I, I, P, P, I, D, P, I, P, I, P, P, P]),
-    "tmdnet_tn_message_bwd": (I, [I, I, I, P, P, I, D, P, I, P, I, P, P, P, P, P]),
-    "tmdnet_tn_message_bwd_add": (I, [I, I, I, P, P, I, D, P, I, P, I, P, P, P, P, P, P]),
+    "tmdnet_tn_message_bwd": (I, [I, I, I, P, P, I, D, P, I, P, I, P, P, P, P, P, P]),
     "tmdnet_tn_message_fwd_pairs": (I, [I, I, I, P, P, I, D, P, I, P, P, I, P, P, P]),
     "tmdnet_tn_message_bwd_pairs": (I, [I, I, I, P, P, I, D, P, I, P, P, I, P, I, P, P, P, P, P, P]),
     "tmdnet_tn_node_fwd": (I, [I, I, I, I, P, P, P, P]),
@@ -113,9 +100,8 @@ SIGNATURES = {
     "tmdnet_pair_prior_fwd": (I, [I, I, I, I, P, P, P, P, P, D, D, D, D, P, P, P]),
     "tmdnet_pair_prior_bwd": (I, [I, I, I, I, P, P, P, P, P, P]),
     "tmdnet_pair_prior_bwd2": (I, [I, I, I, I, I, P, P, P, P, P, P, D, D, D, D, P, P, P, P, P, P]),
-    "tmdnet_dot_sum_fwd": (I, [I, I, I, P, I, P, P, I, P, P, P, P, P]),
+    "tmdnet_dot_sum_fwd": (I, [I, I, I, P, I, P, P, I, P, P, P, P, P, P]),
     "tmdnet_dot_sum_bwd": (I, [I, I, I, P, P, I, P, P, P, P]),
-    "tmdnet_dot_sum_fwd_atoms": (I, [I, I, I, P, I, P, P, I, P, P, P, P, P, P]),
     "tmdnet_layernorm_fwd_f32": (I, [I, I, P, I, P, P, D, P, I, P, P, P]),
     "tmdnet_layernorm_bwd_f32": (I, [I, I, P, I, P, P, P, P, I, P, I, P]),
     "tmdnet_layernorm_bwd2_f32": (I, [I, I, P, I, P, P, P, P, I, P, P, P, P, P, P, P]),
@@ -131,8 +117,7 @@ SIGNATURES = {
     "tmdnet_embedding_fwd_f32": (I, [I, I, I, P, I, P, P, P, P, P]),
     "tmdnet_proj_split_f32": (I, [I, I, P, I, P, P]),
     "tmdnet_split_t_f32": (I, [I, I, P, I, P, P]),
-    "tmdnet_gemm_x3_f32": (I, [I, I, I, P, I, P, P, P, I, I, P]),
-    "tmdnet_gemm_x3_ex_f32": (I, [I, I, I, P, I, P, P, P, I, I, I, P, P, P, I, P]),
+    "tmdnet_gemm_x3_f32": (I, [I, I, I, P, I, P, P, P, I, I, I, P, P, P, I, P]),
     "tmdnet_fep_image_bytes": (SZ, [I, I]),
     "tmdnet_fep_split_f32": (I, [I, I, P, I, P, P, P, P, P]),
     "tmdnet_et_fused_bwd_f32": (I, [I, I, I, I, P, P, I, P, I, P, I, P, I, P, P, P, P, P, P, ctypes.c_longlong, P, P, P,
@@ -148,10 +133,8 @@ SIGNATURES = {
     "tmdnet_eq_head_x3_split_f32": (I, [I, P, P, P]),
     "tmdnet_fep_frags_bytes": (SZ, [ctypes.c_longlong, I]),
     "tmdnet_fep_frags_f32": (I, [ctypes.c_longlong, I, P, P, P, D, D, I, P, P, P]),
-    "tmdnet_proj_f32": (I, [I, I, I, P, I, P, ctypes.c_longlong, P, P, I, P]),
-    "tmdnet_proj_act_f32": (I, [I, I, I, P, P, I, P, ctypes.c_longlong, P, I, P, P, I, P]),
-    "tmdnet_proj_rows_f32": (I, [I, I, I, P, I, P, ctypes.c_longlong, P, P, I, P, P]),
-    "tmdnet_proj_act_rows_f32": (I, [I, I, I, P, P, I, P, ctypes.c_longlong, P, I, P, P, I, P, P]),
+    "tmdnet_proj_f32": (I, [I, I, I, P, I, P, ctypes.c_longlong, P, P, I, P, P]),
+    "tmdnet_proj_act_f32": (I, [I, I, I, P, P, I, P, ctypes.c_longlong, P, I, P, P, I, P, P]),
     "tmdnet_mse2_fwd": (I, [I, I, P, P, D, I, P, P, D, P, P]),
     "tmdnet_mse2_bwd": (I, [I, I, P, P, D, I, P, P, D, P, P, P, P]),
     "tmdnet_build_info": (ctypes.c_char_p, []),

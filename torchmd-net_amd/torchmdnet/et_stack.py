@@ -306,13 +306,13 @@ def _epilogue_fwd(x, vec, vecp, o, veca):
 
 
 def _epilogue_bwd(gx, gvec, vecp, o, g_vecp, g_o, acc=False):
-    """tmdnet_et_epilogue_bwd_acc: g_vecp / g_o written (acc: added to -- they hold injected cotangents)."""
+    """tmdnet_et_epilogue_bwd: g_vecp / g_o written (acc: added to -- they hold injected cotangents)."""
     lib = nat.load()
     N, H = gx.shape
-    rc = lib.tmdnet_et_epilogue_bwd_acc(nat.dtype_code(gx.dtype), N, H, nat.ptr(gx), nat.ptr(gvec),
-                                        nat.ptr(vecp), nat.ptr(o), nat.ptr(g_vecp), nat.ptr(g_o), int(acc),
-                                        nat.stream(gx.device))
-    nat.check(rc, "tmdnet_et_epilogue_bwd_acc")
+    rc = lib.tmdnet_et_epilogue_bwd(nat.dtype_code(gx.dtype), N, H, nat.ptr(gx), nat.ptr(gvec),
+                                    nat.ptr(vecp), nat.ptr(o), nat.ptr(g_vecp), nat.ptr(g_o), int(acc),
+                                    nat.stream(gx.device))
+    nat.check(rc, "tmdnet_et_epilogue_bwd")
 
 
 def _epi_ln(x, vec, vecp, o, veca, ln_w, ln_b, xn_out=None, vo_out=None):
@@ -395,18 +395,18 @@ def _ln_bwd_oproj(g_xn, x, mean, rstd, ln_w, g_res, g_vec, vecp, o, o_w, g_vecp,
 
 
 def _ln_bwd_epi(g_xn, x, mean, rstd, ln_w, g_res, g_vec, vecp, o, g_vecp, g_o, wrows=None, g_res2=None, acc=False):
-    """tmdnet_ln_bwd_epilogue_w: g_x = g_res + LayerNorm backward (g_res None: no residual), then the
+    """tmdnet_ln_bwd_epilogue: g_x = g_res + LayerNorm backward (g_res None: no residual), then the
     previous layer's epilogue backward into g_vecp / g_o (o None: skipped); ``wrows`` (optional
     [N, H]) receives g_xn * xhat, the row terms of the LayerNorm weight gradient; g_res2: a second
     residual term; acc: g_vecp / g_o are added to (they hold injected cotangents)."""
     lib = nat.load()
     N, H = x.shape
     g_x = torch.empty_like(g_xn)
-    rc = lib.tmdnet_ln_bwd_epilogue_w(nat.dtype_code(x.dtype), N, H, nat.ptr(g_xn), nat.ptr(x), nat.ptr(mean),
-                                      nat.ptr(rstd), nat.ptr(ln_w), nat.ptr(g_res), nat.ptr(g_res2), nat.ptr(g_x),
-                                      nat.ptr(g_vec), nat.ptr(vecp), nat.ptr(o), nat.ptr(g_vecp), nat.ptr(g_o),
-                                      nat.ptr(wrows), int(acc), nat.stream(x.device))
-    nat.check(rc, "tmdnet_ln_bwd_epilogue_w")
+    rc = lib.tmdnet_ln_bwd_epilogue(nat.dtype_code(x.dtype), N, H, nat.ptr(g_xn), nat.ptr(x), nat.ptr(mean),
+                                    nat.ptr(rstd), nat.ptr(ln_w), nat.ptr(g_res), nat.ptr(g_res2), nat.ptr(g_x),
+                                    nat.ptr(g_vec), nat.ptr(vecp), nat.ptr(o), nat.ptr(g_vecp), nat.ptr(g_o),
+                                    nat.ptr(wrows), int(acc), nat.stream(x.device))
+    nat.check(rc, "tmdnet_ln_bwd_epilogue")
     return g_x
 
 
@@ -930,7 +930,7 @@ def adjoint_epi_ln_launch(epi, gbar_x_in, gbar_vec_in, ln, outs=None):
     ``epi_adjoint`` / ``ln_adjoint`` restate it (CPU tests).  ``outs`` (optional dict): caller buffers
     "gbgy" (gbar_gy), "gbv" (gbar_vec_out), "wrows" (the per-row weight terms: w_bar is then None and
     the caller sums the rows).  ``gbar_vec_in`` may be a pair (a, b): the cotangent a + b, summed by the
-    kernel (tmdnet_et_adjoint_epi_ln2)."""
+    kernel (tmdnet_et_adjoint_epi_ln)."""
     lib = nat.load()
     outs = outs or {}
     N, H = gbar_x_in.shape
@@ -956,11 +956,11 @@ def adjoint_epi_ln_launch(epi, gbar_x_in, gbar_vec_in, ln, outs=None):
         xbar = torch.empty((N, H), **o_)
     c = lambda t: None if t is None else t.contiguous()  # noqa: E731
     args = [c(t) for t in (gb_o, gb_vecp, gX, gV, vecp, o, gbar_x_in, gbar_vec_in, gbar_vec_in2)]
-    rc = lib.tmdnet_et_adjoint_epi_ln2(nat.dtype_code(gbar_x_in.dtype), N, H, *[nat.ptr(t) for t in args],
-                                       nat.ptr(gbx_out), nat.ptr(gbv_out), nat.ptr(vpbar), nat.ptr(obar),
-                                       *[nat.ptr(c(t)) for t in (x, mean, rstd, w, gy)], nat.ptr(gbgy),
-                                       nat.ptr(xbar), nat.ptr(wrows), nat.stream(gbar_x_in.device))
-    nat.check(rc, "tmdnet_et_adjoint_epi_ln2")
+    rc = lib.tmdnet_et_adjoint_epi_ln(nat.dtype_code(gbar_x_in.dtype), N, H, *[nat.ptr(t) for t in args],
+                                      nat.ptr(gbx_out), nat.ptr(gbv_out), nat.ptr(vpbar), nat.ptr(obar),
+                                      *[nat.ptr(c(t)) for t in (x, mean, rstd, w, gy)], nat.ptr(gbgy),
+                                      nat.ptr(xbar), nat.ptr(wrows), nat.stream(gbar_x_in.device))
+    nat.check(rc, "tmdnet_et_adjoint_epi_ln")
     if epi is None:
         gbx_out = gbar_x_in
         gbv_out = gbar_vec_in if gbar_vec_in2 is None else \
@@ -1500,7 +1500,7 @@ def et_stack(layers, x, graph, f, C, u, rbf=None, out_norm=None, f_pairs=None, f
     (non-trainable) basis, which lets the force pass take its edge gradient straight to r ("dr mode",
     _backward_layers).  ``out_norm`` (nn.LayerNorm(H), the model's final norm) is applied to x inside
     the last layer's epilogue kernel.  ``f_pairs`` = f at the graph's pair rows (``pair_index``
-    numbering), when already produced with f (tmdnet_edge_geom_fwd_rows); else gathered here."""
+    numbering), when already produced with f (tmdnet_edge_geom_fwd); else gathered here."""
     l0 = layers[0]
     H, heads = l0.hidden_channels, l0.num_heads
     hk, hv = l0.dk_proj is not None, l0.dv_proj is not None

@@ -154,7 +154,7 @@ def neighbor_pairs_raw(strategy, pos, batch, box, use_periodic, cutoff_lower, cu
                        pair_rows_out=None):
     """Launch ``tmdnet_nl_build``.  Returns (neighbors, deltas, distances, num_pairs, row_ptr, T).
     ``pairs_out`` = (pair_row [max_pairs], pair_edge [slots]) int32: also number the edge pairs in the
-    same launches (``tmdnet_nl_build_paired_rows``; sorted-row strategies with the transpose map), with the
+    same launches (the build's pair operands; sorted-row strategies with the transpose map), with the
     number of pair rows left in ``pair_rows_out`` (int32 [1], optional)."""
     lib = nat.load()
     nat.require_gpu(pos, "get_neighbor_pairs")
@@ -196,16 +196,12 @@ def neighbor_pairs_raw(strategy, pos, batch, box, use_periodic, cutoff_lower, cu
             float(cutoff_lower), float(cutoff_upper), cap, int(bool(loop)), int(bool(include_transpose)),
             nat.ptr(nb), nat.ptr(dl), nat.ptr(dist), nat.ptr(num), nat.ptr(row_ptr), nat.ptr(tr),
             int(bool(pad_output)), nat.ptr(ws), int(ws.numel()))
-    if pairs_out is not None:
-        pr, pe = pairs_out
-        if tr is None or st == nat.NL_CELL or pr.shape[0] != cap:
-            raise RuntimeError("pair numbering in the build needs sorted rows and the transpose map")
-        rc = lib.tmdnet_nl_build_paired_rows(*args, nat.ptr(pr), nat.ptr(pe), pe.shape[0], nat.ptr(pair_rows_out),
-                                             nat.stream(dev))
-        nat.check(rc, "tmdnet_nl_build_paired_rows")
-    else:
-        rc = lib.tmdnet_nl_build(*args, nat.stream(dev))
-        nat.check(rc, "tmdnet_nl_build")
+    pr, pe = pairs_out if pairs_out is not None else (None, None)
+    if pr is not None and (tr is None or st == nat.NL_CELL or pr.shape[0] != cap):
+        raise RuntimeError("pair numbering in the build needs sorted rows and the transpose map")
+    rc = lib.tmdnet_nl_build(*args, nat.ptr(pr), nat.ptr(pe), 0 if pe is None else pe.shape[0],
+                             nat.ptr(None if pr is None else pair_rows_out), nat.stream(dev))
+    nat.check(rc, "tmdnet_nl_build")
     return nb, dl, dist, num, row_ptr, tr
 
 
@@ -321,7 +317,7 @@ def nl_backward_virial_composite(gd, gr, gr2, deltas, distances, dst, batch, n_m
 
 def nl_backward_virial(pos, gd, gr, gr2, deltas, distances, graph, batch, n_mol):
     """(grad_pos, out [n_mol, 3, 3]) of tmdnet_nl_backward_virial: the neighbour op's position gradient
-    (bitwise tmdnet_nl_backward_multi's) and, from the same row pass, out[m] = sum_e g_e (x) delta_e over the
+    (bitwise tmdnet_nl_backward's) and, from the same row pass, out[m] = sum_e g_e (x) delta_e over the
     edges into molecule m.  Above the entry point's molecule ceiling the row pass runs alone and its
     per-atom sums are added per molecule with index_add, in double as the kernel's own sum stage."""
     lib = nat.load()
@@ -367,11 +363,11 @@ class _NeighborGeomBwd(Function):
             sink.out.add_(w)
         else:
             gpos = torch.empty_like(pos)
-            rc = lib.tmdnet_nl_backward_multi(nat.dtype_code(pos.dtype), n, nat.ptr(graph.row_ptr),
-                                              nat.ptr(graph.transpose), graph.n_edges, nat.ptr(gd), nat.ptr(gr),
-                                              nat.ptr(gr2), nat.ptr(deltas), nat.ptr(distances), nat.ptr(gpos),
-                                              nat.stream(pos.device))
-            nat.check(rc, "tmdnet_nl_backward_multi")
+            rc = lib.tmdnet_nl_backward(nat.dtype_code(pos.dtype), n, nat.ptr(graph.row_ptr),
+                                        nat.ptr(graph.transpose), graph.n_edges, nat.ptr(gd), nat.ptr(gr),
+                                        nat.ptr(gr2), nat.ptr(deltas), nat.ptr(distances), nat.ptr(gpos),
+                                        nat.stream(pos.device))
+            nat.check(rc, "tmdnet_nl_backward")
         ctx.graph = graph
         ctx.two = gr2 is not None
         # the second order sees the summed distance gradient (both slots get its gradient); summed there,
@@ -574,7 +570,7 @@ def _edge_geom_composite(deltas, dist, selfmask, mu, beta, cl, cu, rbf_type, wan
 class _EdgeGeom(Function):
     """(rbf, cutoff, unit vectors) of the graph's edges.  ``fan`` = (k_f, k_c): k_f - 1 more aliases of the
     rbf output and k_c - 1 of the cutoff, one per further consumer; their gradients are summed by the
-    backward kernel (tmdnet_edge_geom_bwd_multi) instead of by autograd add launches."""
+    backward kernel (tmdnet_edge_geom_bwd) instead of by autograd add launches."""
 
     @staticmethod
     def forward(ctx, deltas, dist, graph, mu, beta, cl, cu, rbf_type, want, rows_out=None, fan=(1, 1)):
@@ -586,16 +582,10 @@ class _EdgeGeom(Function):
         u = torch.empty((E, 3), dtype=dist.dtype, device=dist.device) if want[2] else None
         args = (nat.dtype_code(dist.dtype), E, R, rbf_type, nat.ptr(graph.src), nat.ptr(graph.dst), nat.ptr(deltas),
                 nat.ptr(dist), nat.ptr(mu), nat.ptr(beta), float(cl), float(cu), nat.ptr(f), nat.ptr(C), nat.ptr(u))
-        if rows_out is not None:  # also f (and df/dr) at rows (written in place, no autograd: forward-only)
-            rows, frows, drows = rows_out
-            if drows is not None:
-                rc = lib.tmdnet_edge_geom_fwd_rows2(*args, nat.ptr(rows), rows.shape[0], nat.ptr(frows),
-                                                    nat.ptr(drows), nat.stream(dist.device))
-            else:
-                rc = lib.tmdnet_edge_geom_fwd_rows(*args, nat.ptr(rows), rows.shape[0], nat.ptr(frows),
-                                                   nat.stream(dist.device))
-        else:
-            rc = lib.tmdnet_edge_geom_fwd(*args, nat.stream(dist.device))
+        # rows_out: also f (and df/dr) at rows (written in place, no autograd: forward-only)
+        rows, frows, drows = rows_out if rows_out is not None else (None, None, None)
+        rc = lib.tmdnet_edge_geom_fwd(*args, nat.ptr(rows), 0 if rows is None else rows.shape[0], nat.ptr(frows),
+                                      nat.ptr(drows), nat.stream(dist.device))
         nat.check(rc, "tmdnet_edge_geom_fwd")
         ctx.graph = graph
         ctx.cfg = (cl, cu, rbf_type, want)
@@ -650,12 +640,12 @@ class _EdgeGeomBwd(Function):
         gfl = [c(gf), c(gf2), c(gf3)]
         gCl = [c(gC), c(gC2), c(gC3)]
         gu_ = c(gu)
-        rc = lib.tmdnet_edge_geom_bwd_multi(nat.dtype_code(dist.dtype), E, R, rbf_type, nat.ptr(graph.src),
-                                            nat.ptr(graph.dst), nat.ptr(deltas), nat.ptr(dist), nat.ptr(mu),
-                                            nat.ptr(beta), float(cl), float(cu), *[nat.ptr(t) for t in gfl],
-                                            *[nat.ptr(t) for t in gCl], nat.ptr(gu_), nat.ptr(g_r), nat.ptr(g_dl),
-                                            nat.stream(dist.device))
-        nat.check(rc, "tmdnet_edge_geom_bwd_multi")
+        rc = lib.tmdnet_edge_geom_bwd(nat.dtype_code(dist.dtype), E, R, rbf_type, nat.ptr(graph.src),
+                                      nat.ptr(graph.dst), nat.ptr(deltas), nat.ptr(dist), nat.ptr(mu),
+                                      nat.ptr(beta), float(cl), float(cu), *[nat.ptr(t) for t in gfl],
+                                      *[nat.ptr(t) for t in gCl], nat.ptr(gu_), nat.ptr(g_r), nat.ptr(g_dl),
+                                      nat.stream(dist.device))
+        nat.check(rc, "tmdnet_edge_geom_bwd")
         ctx.graph = graph
         ctx.cfg = (cl, cu, rbf_type)
         # the second order sees the summed incoming gradients (each slot's gradient is the same)
@@ -984,12 +974,12 @@ def pair_index_launch(graph, pair_row, pair_edge):
     nrows = None
     if getattr(graph, "static", False):  # the device pair-row count rides on the scan launch
         nrows = torch.empty((1,), dtype=torch.int32, device=pair_row.device)
-    rc = lib.tmdnet_pair_index_rows(n, nat.ptr(graph.row_ptr), nat.ptr(graph.src), nat.ptr(graph.dst),
-                                    nat.ptr(graph.transpose), graph.n_edges, nat.ptr(graph.num_pairs_dev),
-                                    int(getattr(graph, "sorted_rows", False)), nat.ptr(pair_row),
-                                    nat.ptr(pair_edge), pair_edge.shape[0], nat.ptr(nrows), nat.ptr(ws), ws.numel(),
-                                    nat.stream(pair_row.device))
-    nat.check(rc, "tmdnet_pair_index_rows")
+    rc = lib.tmdnet_pair_index(n, nat.ptr(graph.row_ptr), nat.ptr(graph.src), nat.ptr(graph.dst),
+                               nat.ptr(graph.transpose), graph.n_edges, nat.ptr(graph.num_pairs_dev),
+                               int(getattr(graph, "sorted_rows", False)), nat.ptr(pair_row),
+                               nat.ptr(pair_edge), pair_edge.shape[0], nat.ptr(nrows), nat.ptr(ws), ws.numel(),
+                               nat.stream(pair_row.device))
+    nat.check(rc, "tmdnet_pair_index")
     graph.num_pair_rows_dev = nrows
 
 
@@ -1156,14 +1146,14 @@ class _ETMessageBwd(Function):
         return tuple(res) + (None, None, None)
 
 
-# the deterministic source pass of tmdnet_et_message_bwd2_ex stores 7H values per edge: used up to
+# the deterministic source pass of tmdnet_et_message_bwd2 stores 7H values per edge: used up to
 # this scratch size (beyond it the atomic source terms keep the memory flat)
 BWD2_SCRATCH_MAX_BYTES = 2 << 30
 
 
 def et_message_bwd2_launch(q, k, v, vec, pk, pv, C, u, graph, heads, gx, gvec, ggs, flags=0, out=None,
                            pk_rows=None, gg_pkv_scale=None):
-    """One ``tmdnet_et_message_bwd2_ex`` launch: the VJP of tmdnet_et_message_bwd (without the vec
+    """One ``tmdnet_et_message_bwd2`` launch: the VJP of tmdnet_et_message_bwd (without the vec
     residual) at primals (q, k, v, vec, pk, pv, C, u) and seeds (gx, gvec), for the cotangents
     ``ggs`` = (gg_q, gg_k, gg_v, gg_vec, gg_pk, gg_pv, gg_C, gg_u) of its outputs (None / empty =
     zero; node cotangents may be column blocks of a wider buffer).  pk / pv are per-edge rows, or with
@@ -1233,7 +1223,7 @@ def et_message_bwd2_launch(q, k, v, vec, pk, pv, C, u, graph, heads, gx, gvec, g
     qc, kc, vc, pkc, pvc = (_rowmajor(t) for t in (q, k, v, pk, pv))  # read in place through ld
     gxc, gvc = gx.contiguous(), gvec.contiguous()
     P = nat.ptr
-    rc = lib.tmdnet_et_message_bwd2_ex(
+    rc = lib.tmdnet_et_message_bwd2(
         nat.dtype_code(q.dtype), N, H, heads, P(graph.row_ptr), P(graph.src),
         P(graph.transpose if scratch is not None else None), E,
         P(qc), _ld(qc), P(kc), _ld(kc), P(vc), _ld(vc), P(vec), P(pkc), _ld(pkc), P(pvc), _ld(pvc),
@@ -1241,7 +1231,7 @@ def et_message_bwd2_launch(q, k, v, vec, pk, pv, C, u, graph, heads, gx, gvec, g
         P(ggpk), _ld(ggpk), P(ggpv), _ld(ggpv), P(ggC), P(ggu), P(d_gx), P(d_gvec),
         P(d_q), _ld(d_q), P(d_k), _ld(d_k), P(d_v), _ld(d_v), P(d_vec), P(d_pk), _ld(d_pk), P(d_pv), _ld(d_pv),
         P(d_C), P(d_u), P(scratch), P(pk_rows), P(gg_pkv_scale), int(flags), nat.stream(q.device))
-    nat.check(rc, "tmdnet_et_message_bwd2_ex")
+    nat.check(rc, "tmdnet_et_message_bwd2")
     return d_gx, d_gvec, d_q, d_k, d_v, d_vec, d_pk, d_pv, d_C, d_u
 
 
@@ -1852,7 +1842,7 @@ def fused_act(act, x, scale=None):
 
 # ----------------------------------------------------------------------------- dense GEMM
 # C = beta C + A op(B) + bias on one of three back ends: the grouped split-K kernel (tmdnet_gemm_ex_f32, up to
-# 4 problems a launch, up to GEMM_MAX_ROWS rows), the x3 kernel above that (tmdnet_gemm_x3_ex_f32: bf16 MFMA on
+# 4 problems a launch, up to GEMM_MAX_ROWS rows), the x3 kernel above that (tmdnet_gemm_x3_f32: bf16 MFMA on
 # an exact three-piece split, fp32 accuracy), the library.  gemm_group routes plain problems, gemm_ex_launch the ones
 # with an epilogue (no library form); each kernel's envelope is stated once, in *_shape_ok / *_ok below.
 GEMM_UNSUPPORTED = 2
@@ -1878,7 +1868,7 @@ def grouped_shape_ok(M, N, K):
 
 
 def x3_shape_ok(M, N, K):
-    """Shapes tmdnet_gemm_x3_ex_f32 takes (32-wide bf16 MFMA K steps, 16-column output tiles)."""
+    """Shapes tmdnet_gemm_x3_f32 takes (32-wide bf16 MFMA K steps, 16-column output tiles)."""
     return GEMM_BIG == "x3" and M > 0 and K % 32 == 0 and N % 16 == 0
 
 
@@ -1912,7 +1902,7 @@ def grouped_ok(p):
 
 
 def x3_ok(p):
-    """The x3 kernel's envelope (gemm.hip tmdnet_gemm_x3_ex_f32 and the weight splits): 16 bytes throughout."""
+    """The x3 kernel's envelope (gemm.hip tmdnet_gemm_x3_f32 and the weight splits): 16 bytes throughout."""
     return x3_shape_ok(p.A.shape[0], p.C.shape[1], p.A.shape[1]) and _operands_ok(p) and _rows16(p.A) \
         and _rows16(p.B) and _rows16(p.C) and _rows16(p.pre) and _rows16(p.dpre) and _al16(p.bias)
 
@@ -1941,7 +1931,7 @@ def gemm_launch(problems):
 
 
 def gemm_x3(A, B, tb, bias, C, beta, act=0, pre=None, rscale=None, dpre=None):
-    """One Gemm on ``tmdnet_gemm_x3_ex_f32`` for large row counts: B's three bf16 pieces split once per call
+    """One Gemm on ``tmdnet_gemm_x3_f32`` for large row counts: B's three bf16 pieces split once per call
     (tmdnet_proj_split_f32 for a [N][K] weight, tmdnet_split_t_f32 for a [K][N] right operand).  Returns False
     (nothing launched) outside its envelope (x3_ok)."""
     if not x3_ok(Gemm(A, B, tb, bias, C, beta, act, pre, rscale, dpre)):
@@ -1958,11 +1948,11 @@ def gemm_x3(A, B, tb, bias, C, beta, act=0, pre=None, rscale=None, dpre=None):
     if rc == GEMM_UNSUPPORTED:
         return False
     nat.check(rc, "tmdnet_split")
-    rc = lib.tmdnet_gemm_x3_ex_f32(M, N, K, A.data_ptr(), A.stride(0), bp.data_ptr(), nat.ptr(bias), C.data_ptr(),
-                                   C.stride(0), *epi, st)
+    rc = lib.tmdnet_gemm_x3_f32(M, N, K, A.data_ptr(), A.stride(0), bp.data_ptr(), nat.ptr(bias), C.data_ptr(),
+                                C.stride(0), *epi, st)
     if rc == GEMM_UNSUPPORTED:
         return False
-    nat.check(rc, "tmdnet_gemm_x3_ex_f32")
+    nat.check(rc, "tmdnet_gemm_x3_f32")
     return True
 
 
@@ -2039,7 +2029,7 @@ def proj(A, W, bias=None, out=None, wp=None, row0=0, *, rows=None):
     16-byte aligned rows, N % 16 == 0); anything else, fp64 parity runs and ``TMDNET_PROJ=lib`` use
     the library GEMM on the same device.  ``wp``: W's split from ``proj_split`` when the caller shares
     it between GEMMs (W = rows [row0, row0 + N) of the split weight); ``out`` receives the result.
-    ``rows``: an int32 [1] device row count (``tmdnet_proj_rows_f32``) -- the kernel writes the rows below min(M, max(0, rows)) only,
+    ``rows``: an int32 [1] device row count -- the kernel writes the rows below min(M, max(0, rows)) only,
     the others keep what the buffer held (every reader must be index-driven or row-counted); the library
     path computes every row."""
     M, K = A.shape
@@ -2053,13 +2043,10 @@ def proj(A, W, bias=None, out=None, wp=None, row0=0, *, rows=None):
         if wp is not None:
             args = (M, N, K, A.data_ptr(), A.stride(0), wp[0, row0:].data_ptr(), wp.shape[1] * K,
                     None if bias is None else bias.data_ptr(), out.data_ptr(), out.stride(0))
-            if rows is None:
-                name, rc = "tmdnet_proj_f32", nat.load().tmdnet_proj_f32(*args, nat.stream(A.device))
-            else:
-                name, rc = "tmdnet_proj_rows_f32", nat.load().tmdnet_proj_rows_f32(
-                    *args, _rows_ptr(rows, A.device), nat.stream(A.device))
+            rc = nat.load().tmdnet_proj_f32(*args, None if rows is None else _rows_ptr(rows, A.device),
+                                            nat.stream(A.device))
             if rc != GEMM_UNSUPPORTED:
-                nat.check(rc, name)
+                nat.check(rc, "tmdnet_proj_f32")
                 return out
     return gemm_lib(Gemm(A, W, True, bias, out, False))
 
@@ -2093,14 +2080,11 @@ def proj_act(A, dA, W, bias, act, wp=None, row0=0, out=None, *, rows=None):
     args = (M, N, K, A.data_ptr(), None if dA is None else dA.data_ptr(), A.stride(0), wp[0, row0:].data_ptr(),
             wp.shape[1] * K, None if bias is None else bias.data_ptr(), int(act), S.data_ptr(),
             None if D is None else D.data_ptr(), S.stride(0))
-    if rows is None:
-        name, rc = "tmdnet_proj_act_f32", nat.load().tmdnet_proj_act_f32(*args, nat.stream(A.device))
-    else:
-        name, rc = "tmdnet_proj_act_rows_f32", nat.load().tmdnet_proj_act_rows_f32(
-            *args, _rows_ptr(rows, A.device), nat.stream(A.device))
+    rc = nat.load().tmdnet_proj_act_f32(*args, None if rows is None else _rows_ptr(rows, A.device),
+                                        nat.stream(A.device))
     if rc == GEMM_UNSUPPORTED:
         return None
-    nat.check(rc, name)
+    nat.check(rc, "tmdnet_proj_act_f32")
     return S, D
 
 
@@ -2389,13 +2373,13 @@ def pair_prior(kind, graph, a, b, consts, batch, n_mol):
 
 
 def _dot_sum_launch(h, w, b0, batch, n_mol, std, mean):
-    """y[b] = mean + std * sum_{batch[n] = b} (h[n] . w + b0), one tmdnet_dot_sum_fwd_atoms launch."""
+    """y[b] = mean + std * sum_{batch[n] = b} (h[n] . w + b0), one tmdnet_dot_sum_fwd launch."""
     y = torch.empty((n_mol, 1), dtype=h.dtype, device=h.device)
     # large systems: the row products over the whole grid first (per-atom buffer)
     buf = torch.empty(h.shape[0], dtype=h.dtype, device=h.device) if h.shape[0] > 4096 else None
-    rc = nat.load().tmdnet_dot_sum_fwd_atoms(nat.dtype_code(h.dtype), h.shape[0], h.shape[1], nat.ptr(h), h.stride(0),
-                                             nat.ptr(w), nat.ptr(b0), n_mol, nat.ptr(batch), nat.ptr(std),
-                                             nat.ptr(mean), nat.ptr(buf), nat.ptr(y), nat.stream(h.device))
+    rc = nat.load().tmdnet_dot_sum_fwd(nat.dtype_code(h.dtype), h.shape[0], h.shape[1], nat.ptr(h), h.stride(0),
+                                       nat.ptr(w), nat.ptr(b0), n_mol, nat.ptr(batch), nat.ptr(std),
+                                       nat.ptr(mean), nat.ptr(buf), nat.ptr(y), nat.stream(h.device))
     nat.check(rc, "tmdnet_dot_sum_fwd")
     return y
 
@@ -2605,10 +2589,10 @@ def tn_message_bwd_launch(ea, Tc, graph, gmsg, gea, gT, gadd=None, pairs=None):
                                              nat.ptr(gT), nat.stream(Tc.device))
         nat.check(rc, "tmdnet_tn_message_bwd_pairs")
         return
-    rc = lib.tmdnet_tn_message_bwd_add(nat.dtype_code(Tc.dtype), N, H, nat.ptr(graph.row_ptr), nat.ptr(graph.src),
-                                       graph.n_edges, *_self0_args(graph), nat.ptr(ea), _ld(ea), nat.ptr(Tc),
-                                       nat.ptr(gmsg), nat.ptr(gadd), nat.ptr(gea), nat.ptr(gT), nat.stream(Tc.device))
-    nat.check(rc, "tmdnet_tn_message_bwd_add")
+    rc = lib.tmdnet_tn_message_bwd(nat.dtype_code(Tc.dtype), N, H, nat.ptr(graph.row_ptr), nat.ptr(graph.src),
+                                   graph.n_edges, *_self0_args(graph), nat.ptr(ea), _ld(ea), nat.ptr(Tc),
+                                   nat.ptr(gmsg), nat.ptr(gadd), nat.ptr(gea), nat.ptr(gT), nat.stream(Tc.device))
+    nat.check(rc, "tmdnet_tn_message_bwd")
 
 
 def _ea_edges(ea, pairs):
