@@ -74,8 +74,14 @@ enum { TMDNET_ACT_SILU = 0, TMDNET_ACT_SSP = 1, TMDNET_ACT_TANH = 2, TMDNET_ACT_
  * transpose_map (int32[max_pairs], nullable) receives T[e] = index of the reversed edge (or -1);
  * only meaningful when include_transpose=1.
  * box9: row-major 3x3 box vectors on the HOST (reduced triclinic form), may be NULL if not periodic.
- * The cell strategy needs a diagonal box (the caller supplies 3*cutoff when not periodic, as
- * reference utils.py:199-202 does).
+ * The cell strategy takes any periodic box of that form (rows a = (a0,0,0), b = (b0,b1,0), c = (c0,c1,c2)).
+ * A diagonal box is binned along x, y, z with the rectangular wrap (the reference cell list); a box with a
+ * non-zero b0, c0 or c1 is binned in fractional coordinates over max(3, floor(w_i / cutoff)) cells per
+ * lattice axis, w_i the perpendicular widths V/|b x c|, V/|c x a|, V/|a x b|, and its pairs are those of
+ * the brute strategy (same minimum image, bitwise the same deltas).  More than 1024 cells on an axis:
+ * TMDNET_UNSUPPORTED.  Not periodic, the cell strategy needs a diagonal box (the caller supplies
+ * 3*cutoff, as reference utils.py:199-202 does); a non-diagonal one is TMDNET_BAD_ARGUMENT.
+ * tmdnet_nl_workspace_bytes sizes the cell arrays by the same rule from box9.
  * Pair numbering (optional): pair_row [max_pairs] and pair_edge [n_pair_slots > 0] given together are filled
  * as tmdnet_pair_index fills them, with no extra launch (the canonical counts ride on the count pass, their
  * scan on the row scan, the numbers on the transpose pass).  It needs sorted rows and the reversed edges:

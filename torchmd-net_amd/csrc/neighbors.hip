@@ -18,6 +18,9 @@
 //    batches fall back to scanning every atom.
 //  * The cell strategy bins atoms (rect PBC, reference cell geometry), stable-radix-sorts them by
 //    cell (deterministic within-cell order), then runs the same count/fill pair over the 27 cells.
+//    A periodic box with a skew entry (the reference's cell list refuses it) is binned in fractional
+//    coordinates along the lattice directions instead; its pairs are accepted with the triclinic
+//    minimum image of brute / shared, so the list holds brute's pairs with bitwise brute's deltas.
 //  * An optional transpose map T (T[e] = index of the reversed edge) lets the backward pass be a
 //    segmented CSR reduction with no atomics:  dpos[n] = sum_{e in row n} g[T(e)] - g[e].
 #include "common.h"
@@ -322,6 +325,7 @@ template <typename T> struct CellGeom {
   V3<T> L;
   T cut;
   int nx, ny, nz;
+  Tric<T> box;  // TRIC kernels only: the lattice the fractional coordinates are taken in
 };
 
 // One axis of the reference getCell (neighbors_cuda_cell.cuh:38-55): shift the wrapped coordinate by
@@ -346,13 +350,40 @@ __device__ __forceinline__ void cell_of(const CellGeom<T>& G, V3<T> p, int& cx, 
   cz = cell_axis(p.z, G.L.z, G.cut, G.nz);
 }
 
+// Triclinic box: one lattice axis, from the fractional coordinate s (any real number; the cell of
+// s - floor(s) in [0, 1) scaled by the cell count).  s - floor(s) rounds to 1 for a tiny negative s and
+// s * n can round up to n one ulp below the top face: both sit on the periodic face and go to cell 0
+// (cells 0 and n - 1 scan each other).  Like cell_axis, every other value -- a coordinate past the
+// box's fp resolution, a non-finite one (NaN compares false) -- is forced into [0, n): the keys index
+// cstart/cend unchecked.
+template <typename T> __device__ __forceinline__ int cell_frac(T s, int n) {
+  const T f = floor((s - floor(s)) * T(n));
+  if (!(f < T(n))) return 0;
+  return f < T(0) ? n - 1 : (int)f;
+}
+
+// Fractional coordinates by forward substitution through the lower-triangular box (rows a, b, c):
+// p = sx a + sy b + sz c.  Every operation is rounded on its own (no fma contraction), so that the
+// binning is a function of the position that tests/neighbor_cases_tric.py restates exactly.
 template <typename T>
+__device__ __forceinline__ void cell_of_tric(const CellGeom<T>& G, V3<T> p, int& cx, int& cy, int& cz) {
+#pragma clang fp contract(off)
+  const T sz = p.z / G.box.c2;
+  const T sy = (p.y - sz * G.box.c1) / G.box.b1;
+  const T sx = (p.x - sz * G.box.c0 - sy * G.box.b0) / G.box.a0;
+  cx = cell_frac(sx, G.nx);
+  cy = cell_frac(sy, G.ny);
+  cz = cell_frac(sz, G.nz);
+}
+
+template <typename T, bool TRIC>
 __global__ void k_cell_assign(const T* __restrict__ pos, int n, CellGeom<T> G, int* __restrict__ keys,
                               int* __restrict__ vals) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   int cx, cy, cz;
-  cell_of(G, load3(pos, i), cx, cy, cz);
+  if (TRIC) cell_of_tric(G, load3(pos, i), cx, cy, cz);
+  else cell_of(G, load3(pos, i), cx, cy, cz);
   keys[i] = cx + G.nx * (cy + G.ny * cz);
   vals[i] = i;
 }
@@ -369,7 +400,11 @@ __global__ void k_cell_bounds(const int* __restrict__ skeys, int n, int* __restr
 // One thread per atom, visited in cell-sorted order (neighbouring threads share cells).  Candidate
 // order inside a row: the 27 cell offsets in the reference order (_cell.cuh:187-195), then the
 // stable-sorted (ascending atom index) members of each cell -> deterministic.
-template <typename T, bool FILL>
+// TRIC: the cells are those of cell_of_tric, the offsets run along the lattice directions and accept()
+// wraps with the triclinic image (P.rect == 0).  A source within the cutoff of t has every fractional
+// coordinate within cutoff / w_i <= 1 / n_i of t's (w_i the cell's perpendicular width), so it lies in
+// one of the 27 cells; with n_i == 3 the three offsets are the whole axis.  n_i >= 3 keeps the 27 distinct.
+template <typename T, bool FILL, bool TRIC>
 __global__ __launch_bounds__(256) void k_cell_pairs(Params<T> P, CellGeom<T> G,
                                                     const int* __restrict__ skeys,
                                                     const int* __restrict__ svals,
@@ -385,7 +420,8 @@ __global__ __launch_bounds__(256) void k_cell_pairs(Params<T> P, CellGeom<T> G,
   const V3<T> pt = load3(P.pos, t);
   const int64_t bt = P.batch[t];
   int cx, cy, cz;
-  cell_of(G, pt, cx, cy, cz);
+  if (TRIC) cell_of_tric(G, pt, cx, cy, cz);
+  else cell_of(G, pt, cx, cy, cz);
   int off = FILL ? row_ptr[t] : 0;
   for (int k = 0; k < 27; ++k) {
     int jx = cx + k % 3 - 1, jy = cy + (k / 3) % 3 - 1, jz = cz + k / 9 - 1;
@@ -633,12 +669,33 @@ struct CellDims {
   int nx, ny, nz;
 };
 
+// A box with a skew entry (b0, c0 or c1): the triclinic cell path when periodic.
+static bool box_skewed(const double* box) { return box[3] != 0 || box[6] != 0 || box[7] != 0; }
+
+// Cells per axis: max(3, floor(extent / cutoff)), at most 1024.  The extent of a diagonal box is its edge
+// length; of a skewed one (rows a = (a0,0,0), b = (b0,b1,0), c = (c0,c1,c2), V = a0 b1 c2) the
+// perpendicular width along each lattice direction, V/|b x c|, V/|c x a|, V/|a x b| = c2: with
+// floor(w / cutoff) >= 4 cells, a cell is at least one cutoff thick between its faces.  layout() and
+// build() both size the grid here; on an error the grid is left 3 x 3 x 3.
 static int cell_dims(const double* box, double cut, CellDims& cd) {
-  auto f = [&](double l) { int c = (int)(l / cut); return c < 3 ? 3 : c; };
-  cd.nx = f(box[0]);
-  cd.ny = f(box[4]);
-  cd.nz = f(box[8]);
-  if (cd.nx > 1024 || cd.ny > 1024 || cd.nz > 1024) return kUnsupported;
+  cd = {3, 3, 3};
+  double w[3] = {box[0], box[4], box[8]};
+  if (box_skewed(box)) {
+    const double a0 = box[0], b0 = box[3], b1 = box[4], c0 = box[6], c1 = box[7], c2 = box[8];
+    const double bc[3] = {b1 * c2, -b0 * c2, b0 * c1 - b1 * c0};  // b x c;  c x a = a0 (0, c2, -c1)
+    w[0] = fabs(a0 * b1 * c2) / sqrt(bc[0] * bc[0] + bc[1] * bc[1] + bc[2] * bc[2]);
+    w[1] = fabs(b1 * c2) / sqrt(c1 * c1 + c2 * c2);
+    w[2] = fabs(c2);
+    for (double v : w)
+      if (!(v > 0) || !(v < 1e300)) return kBadArgument;  // a degenerate or non-finite cell
+  }
+  int c[3];
+  for (int i = 0; i < 3; ++i) {
+    const double q = w[i] / cut;
+    if (q >= 1025) return kUnsupported;  // more than 1024 cells (asked before the conversion: q may not fit an int)
+    c[i] = q >= 3 ? (int)q : 3;
+  }
+  cd = {c[0], c[1], c[2]};
   return kOk;
 }
 
@@ -665,7 +722,7 @@ static Layout layout(int n, int strategy, const double* box, double cut) {
   L.cc = o; o += align16(sizeof(int) * ((size_t)n + 1));
   L.pairp = o; o += align16(sizeof(int) * ((size_t)n + 1));
   if (strategy == TMDNET_NL_CELL) {
-    CellDims cd{3, 3, 3};
+    CellDims cd;
     cell_dims(box, cut, cd);
     L.ncells = cd.nx * cd.ny * cd.nz;
     L.keys = o; o += align16(sizeof(int) * (size_t)n);
@@ -704,7 +761,10 @@ static int build(int strategy, const T* pos, const int64_t* batch, int n, const 
   P.batch = batch;
   P.n = n;
   P.periodic = periodic;
-  P.rect = strategy == TMDNET_NL_CELL;
+  // the cell list of a periodic skewed box: fractional-coordinate cells, the triclinic image of brute
+  const bool tric = strategy == TMDNET_NL_CELL && periodic && box_skewed(box);
+  if (strategy == TMDNET_NL_CELL && !periodic && box_skewed(box)) return kBadArgument;
+  P.rect = strategy == TMDNET_NL_CELL && !tric;
   if (periodic || strategy == TMDNET_NL_CELL) {
     P.box = {(T)box[0], (T)box[3], (T)box[4], (T)box[6], (T)box[7], (T)box[8]};
     P.L = {(T)box[0], (T)box[4], (T)box[8]};
@@ -718,15 +778,18 @@ static int build(int strategy, const T* pos, const int64_t* batch, int n, const 
   const int tb = 256;
   if (strategy == TMDNET_NL_CELL) {
     CellDims cd;
-    if (cell_dims(box, cu, cd) != kOk) return kUnsupported;
-    CellGeom<T> G{{(T)box[0], (T)box[4], (T)box[8]}, cuT, cd.nx, cd.ny, cd.nz};
+    if (const int rc = cell_dims(box, cu, cd)) return rc;
+    CellGeom<T> G{{(T)box[0], (T)box[4], (T)box[8]}, cuT, cd.nx, cd.ny, cd.nz, P.box};
     int* keys = (int*)(ws + Lo.keys);
     int* vals = (int*)(ws + Lo.vals);
     int* skeys = (int*)(ws + Lo.skeys);
     int* svals = (int*)(ws + Lo.svals);
     int* cstart = (int*)(ws + Lo.cstart);
     int* cend = (int*)(ws + Lo.cend);
-    hipLaunchKernelGGL(k_cell_assign<T>, dim3((n + tb - 1) / tb), dim3(tb), 0, st, pos, n, G, keys, vals);
+    if (tric)
+      hipLaunchKernelGGL((k_cell_assign<T, true>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, pos, n, G, keys, vals);
+    else
+      hipLaunchKernelGGL((k_cell_assign<T, false>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, pos, n, G, keys, vals);
     size_t cb = Lo.cub_bytes;
     int endbit = 1;
     while ((1 << endbit) < Lo.ncells && endbit < 31) ++endbit;
@@ -735,12 +798,20 @@ static int build(int strategy, const T* pos, const int64_t* batch, int n, const 
       return kLaunchFailed;
     TMD_CHECK(hipMemsetAsync(cstart, 0xFF, sizeof(int) * (size_t)Lo.ncells, st));
     hipLaunchKernelGGL(k_cell_bounds, dim3((n + tb - 1) / tb), dim3(tb), 0, st, skeys, n, cstart, cend);
-    hipLaunchKernelGGL((k_cell_pairs<T, false>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, P, G, skeys,
-                       svals, cstart, cend, counts, row_ptr, cap, nb, dlt, dist);
+    if (tric)
+      hipLaunchKernelGGL((k_cell_pairs<T, false, true>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, P, G, skeys,
+                         svals, cstart, cend, counts, row_ptr, cap, nb, dlt, dist);
+    else
+      hipLaunchKernelGGL((k_cell_pairs<T, false, false>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, P, G, skeys,
+                         svals, cstart, cend, counts, row_ptr, cap, nb, dlt, dist);
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, counts, n, row_ptr, num_pairs, nullptr, nullptr,
                        cap, 0, nullptr);
-    hipLaunchKernelGGL((k_cell_pairs<T, true>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, P, G, skeys,
-                       svals, cstart, cend, counts, row_ptr, cap, nb, dlt, dist);
+    if (tric)
+      hipLaunchKernelGGL((k_cell_pairs<T, true, true>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, P, G, skeys,
+                         svals, cstart, cend, counts, row_ptr, cap, nb, dlt, dist);
+    else
+      hipLaunchKernelGGL((k_cell_pairs<T, true, false>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, P, G, skeys,
+                         svals, cstart, cend, counts, row_ptr, cap, nb, dlt, dist);
     if (tr || pad)
       hipLaunchKernelGGL((k_transpose<T, false>), dim3((cap + tb - 1) / tb), dim3(tb), 0, st, nb, row_ptr, cap,
                          num_pairs, tr, pad, dlt, dist, PR);

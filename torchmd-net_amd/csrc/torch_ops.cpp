@@ -155,7 +155,9 @@ Built nl_build(const std::string& strategy_in, const Tensor& pos, const Tensor& 
   }
   if (st == TMDNET_NL_CELL) {
     TORCH_CHECK(have_box, "Expected \"box_size\" to have shape (3, 3)");
-    TORCH_CHECK(box9[1] == 0 && box9[2] == 0 && box9[3] == 0 && box9[5] == 0 && box9[6] == 0 && box9[7] == 0,
+    // periodic: any box validate_box passed (a skewed one takes the triclinic cell path of tmdnet_nl_build)
+    TORCH_CHECK(use_periodic ||
+                    (box9[1] == 0 && box9[2] == 0 && box9[3] == 0 && box9[5] == 0 && box9[6] == 0 && box9[7] == 0),
                 "Expected \"box_size\" to be diagonal");
   }
   const int cap = static_cast<int>(max_pairs);
@@ -1780,9 +1782,18 @@ Tensor spatial_permutation(const Tensor& pos, const Tensor& batch, double cell, 
   if (periodic && box.defined() && box.numel() == 9) {
     Tensor b = box.detach().to(at::kCPU).to(at::kDouble).contiguous();
     const double* bd = b.data_ptr<double>();
-    p = at::stack({at::remainder(p.select(1, 0), bd[0]), at::remainder(p.select(1, 1), bd[4]),
-                   at::remainder(p.select(1, 2), bd[8])},
-                  1);
+    if (bd[3] == 0 && bd[6] == 0 && bd[7] == 0) {
+      p = at::stack({at::remainder(p.select(1, 0), bd[0]), at::remainder(p.select(1, 1), bd[4]),
+                     at::remainder(p.select(1, 2), bd[8])},
+                    1);
+    } else {  // triclinic: whole box vectors off, by the floor of the fractional coordinates (kernels.wrap_into_box)
+      Tensor x = p.select(1, 0), y = p.select(1, 1), z = p.select(1, 2);
+      Tensor sz = z / bd[8];
+      Tensor sy = (y - sz * bd[7]) / bd[4];
+      Tensor sx = (x - sz * bd[6] - sy * bd[3]) / bd[0];
+      Tensor kx = at::floor(sx), ky = at::floor(sy), kz = at::floor(sz);
+      p = at::stack({x - kx * bd[0] - ky * bd[3] - kz * bd[6], y - ky * bd[4] - kz * bd[7], z - kz * bd[8]}, 1);
+    }
   }
   Tensor lo = std::get<0>(p.min(0));
   Tensor c = at::clamp(((p - lo) / cell).to(at::kLong), 0, 1023);

@@ -183,7 +183,9 @@ def neighbor_pairs_raw(strategy, pos, batch, box, use_periodic, cutoff_lower, cu
             raise RuntimeError('Expected "box_size" to have shape (3, 3)')
         b = list(box9)
         if any(b[i] != 0 for i in (1, 2, 3, 5, 6, 7)):
-            raise RuntimeError('Expected "box_size" to be diagonal')
+            if not use_periodic:
+                raise RuntimeError('Expected "box_size" to be diagonal')
+            validate_box(box, cutoff_upper)  # reduced triclinic form: the build's triclinic cell path
     ws_bytes = lib.tmdnet_nl_workspace_bytes(n, st, box9, float(cutoff_upper))
     ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=dev)
     nb = torch.empty((2, cap), dtype=torch.int32, device=dev)
@@ -2804,6 +2806,24 @@ def _spread10(x):
     return x
 
 
+def wrap_into_box(pos, box):
+    """``pos`` [N, 3] (any device) moved into the parallelepiped of ``box`` (host 3x3, rows a = (a0,0,0),
+    b = (b0,b1,0), c = (c0,c1,c2)) by integer combinations of the box rows: the fractional coordinates of
+    the result lie in [0, 1).  The box enters as Python scalars, so no host-to-device copy is issued (not
+    allowed inside a graph capture).  A diagonal box gives ``torch.remainder`` per axis."""
+    v = box.detach().cpu().double().tolist()
+    (a0, _, _), (b0, b1, _), (c0, c1, c2) = v
+    if b0 == 0 and c0 == 0 and c1 == 0:
+        return torch.stack([torch.remainder(pos[:, i], float(L)) for i, L in enumerate((a0, b1, c2))], dim=1)
+    # fractional coordinates by forward substitution (pos = sx a + sy b + sz c), as the cell build's binning
+    x, y, z = pos[:, 0], pos[:, 1], pos[:, 2]
+    sz = z / c2
+    sy = (y - sz * c1) / b1
+    sx = (x - sz * c0 - sy * b0) / a0
+    kx, ky, kz = torch.floor(sx), torch.floor(sy), torch.floor(sz)
+    return torch.stack([x - kx * a0 - ky * b0 - kz * c0, y - ky * b1 - kz * c1, z - kz * c2], dim=1)
+
+
 def spatial_permutation(pos, batch, cell_size, box=None):
     """Permutation that renumbers atoms molecule-major, then by the Morton (Z-order) index of their
     cutoff-sized cell.  Edge kernels gather source rows of spatial neighbours; with this numbering
@@ -2811,10 +2831,9 @@ def spatial_permutation(pos, batch, cell_size, box=None):
     C5 water box vs random numbering (tools/kbench.py).  Sync-free (device argsort)."""
     p = pos.detach()
     if box is not None and box.numel() == 9:
-        # the box lives in host memory (reference OptimizedDistance keeps it on the CPU): its diagonal as
-        # Python scalars, so no host-to-device copy is issued (not allowed inside a graph capture)
-        L = torch.diagonal(box.detach().cpu()).tolist()
-        p = torch.stack([torch.remainder(p[:, i], float(L[i])) for i in range(3)], dim=1)
+        # the box lives in host memory (reference OptimizedDistance keeps it on the CPU) and enters as
+        # Python scalars; a triclinic cell is made compact too (the Morton cells stay Cartesian)
+        p = wrap_into_box(p, box)
     lo = p.min(dim=0).values
     c = torch.clamp(((p - lo) / float(cell_size)).long(), 0, 1023)
     key = _spread10(c[:, 0]) | (_spread10(c[:, 1]) << 1) | (_spread10(c[:, 2]) << 2)
