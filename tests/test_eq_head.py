@@ -59,14 +59,16 @@ def _rel(a, b):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("nt", ["1", "2"])  # atoms per workgroup (TMDNET_HEAD_NT; 2 from 2k atoms)
+@pytest.mark.parametrize("nt", ["1", "2"])  # atoms per workgroup, by the atom count (2 from 2048 atoms)
 @pytest.mark.parametrize("dtype,H,tol", [(torch.float64, 128, 1e-11), (torch.float32, 128, 2e-5),
                                          (torch.float64, 48, 1e-11), (torch.float32, 256, 2e-5)])
 def test_hip_head_matches_composite(dtype, H, tol, nt, monkeypatch):
-    monkeypatch.setenv("TMDNET_HEAD_NT", nt)
+    # (TMDNET_HEAD_NT is read once per process: setting it here would reach only the first case.  The env-only
+    # form of 4 atoms runs in a child process, tests/test_gpu_eq_head_widths.py)
+    monkeypatch.setattr(kernels, "HEAD_X3", False)  # the per-atom kernel at 2049 atoms too
     head = _head(H, dtype).to(DEV)
     ps = kernels.eq_head_params(head.output_network)
-    N = 37  # not a multiple of the atom tile
+    N = {"1": 37, "2": 2049}[nt]  # neither a multiple of the atom tile
     x, vec = _inputs(N, H, dtype, DEV)
     x.requires_grad_(True)
     vec.requires_grad_(True)

@@ -54,6 +54,11 @@ class _HeadLink:
         _HEAD_HANDED.append(weakref.ref(self))
 
 
+def _no_node():
+    """A _HeadLink side that will not run (the HVP fell back to the composite and leaves no factor rows)."""
+    return None
+
+
 def head_pending_left():
     """Number of head links whose handed-off factor rows were never consumed (and drop them)."""
     left = [m for m in (r() for r in _HEAD_HANDED) if m is not None and m.pending is not None]
@@ -2851,9 +2856,15 @@ def eq_head_params(blocks):
     return ps
 
 
+# widest head tmdnet_eq_head_fwd / _bwd_weights take: one atom's buffers (csrc/eq_head.hip Layout, 29.5 H + 8
+# values) in 64 KB of LDS.  The library's own answer at both ends is pinned in tests/test_gpu_eq_head_widths.py.
+HEAD_MAX_HIDDEN = {torch.float32: 552, torch.float64: 276}
+
+
 def eq_head_fusable(blocks):
     """Two GatedEquivariantBlocks H -> H/2 (scalar SiLU) -> 1, SiLU update nets, intermediate = hidden
-    (EquivariantScalar's configuration, reference output_modules.py:80-100)."""
+    (EquivariantScalar's configuration, reference output_modules.py:80-100), no wider than the kernel takes
+    (wider heads run module by module)."""
     if len(blocks) != 2:
         return False
     b1, b2 = blocks
@@ -2863,7 +2874,8 @@ def eq_head_fusable(blocks):
                  and b1.update_net[0].out_features == H and b2.update_net[0].out_features == H // 2)
     acts_ok = all(isinstance(b.update_net[1], torch.nn.SiLU) for b in blocks) \
         and isinstance(b1.act, torch.nn.SiLU) and b2.act is None
-    return bool(shapes_ok and acts_ok and all(b.update_net[0].bias is not None for b in blocks))
+    width_ok = H <= HEAD_MAX_HIDDEN.get(b1.vec1_proj.weight.dtype, H)
+    return bool(shapes_ok and acts_ok and width_ok and all(b.update_net[0].bias is not None for b in blocks))
 
 
 def masked_norm(vb):
@@ -3062,6 +3074,7 @@ class _EqHeadBwd(Function):
     def backward(ctx, ggx, ggv, *ggp):
         saved = ctx.saved_tensors
         _create = torch.is_grad_enabled()  # third order only if the caller builds a graph
+        fwd_rows = None
         if not _create and all(g is None for g in ggp) and HEAD_SECOND_ORDER != "composite":
             gy, x, vec, *params = saved
             need_p = [ctx.needs_input_grad[6 + i] for i in range(len(params))]
@@ -3070,13 +3083,21 @@ class _EqHeadBwd(Function):
             link = getattr(ctx, "link", None) if (any(need_p) and HEAD_HANDOFF) else None
             seg2 = link.take("hvp") if link is not None else None
             hand = link is not None and seg2 is None and link.other_will_run("hvp")
-            d_gy, d_x, d_vec, d_p = eq_head_hvp(x, vec, params, gy, ggx, ggv, ctx.needs_input_grad[1], any(need_p),
-                                                factors_only=hand, seg2=seg2)
-            if hand:
-                link.leave("hvp", d_p)
-                d_p = None
-            d_p = [g if w else None for g, w in zip(d_p, need_p)] if d_p is not None else [None] * len(params)
-            return (None, d_gy, None, None, d_x, d_vec) + tuple(d_p)
+            res = eq_head_hvp(x, vec, params, gy, ggx, ggv, ctx.needs_input_grad[1], any(need_p),
+                              factors_only=hand, seg2=seg2)
+            if res is not None:
+                d_gy, d_x, d_vec, d_p = res
+                if hand:
+                    link.leave("hvp", d_p)
+                    d_p = None
+                d_p = [g if w else None for g, w in zip(d_p, need_p)] if d_p is not None else [None] * len(params)
+                return (None, d_gy, None, None, d_x, d_vec) + tuple(d_p)
+            # wider than the HVP kernel takes: the composite below.  It leaves no factor rows, so the forward
+            # node must not wait for them (it forms its own weight gradients), and rows it already left are
+            # summed here
+            fwd_rows = seg2
+            if link is not None:
+                link.hvp = _no_node
         with torch.enable_grad():
             leaves = [t.detach().requires_grad_(True) for t in saved]
             gy, x, vec = leaves[:3]
@@ -3089,7 +3110,11 @@ class _EqHeadBwd(Function):
             second = torch.autograd.grad([f for f, _ in sel], leaves, [g for _, g in sel],
                                          create_graph=_create, allow_unused=True)
         d_gy, d_x, d_vec = second[:3]
-        return (None, d_gy, None, None, d_x, d_vec) + tuple(second[3:])
+        d_p = second[3:]
+        if fwd_rows is not None:
+            own = _head_wgrads(fwd_rows[0], x.shape[1], *fwd_rows[1])
+            d_p = [o if g is None else g + o for g, o in zip(d_p, own)]
+        return (None, d_gy, None, None, d_x, d_vec) + tuple(d_p)
 
 
 def eq_head_hvp(x, vec, params, gy, tx, tv, want_gy=True, want_w=True, factors_only=False, seg2=None):
@@ -3098,7 +3123,8 @@ def eq_head_hvp(x, vec, params, gy, tx, tv, want_gy=True, want_w=True, factors_o
     of (g_x, g_vec) = gy * J(x, vec); each weight term is one GEMM over the kernel's per-atom
     factors ([tangent rows ; plain rows], the layouts of _eq_head_weight_grads).  ``factors_only``:
     the fourth item is (2N, factor rows) for _head_wgrads' seg2 instead of the weight terms; ``seg2``:
-    the first-order pass's factor rows, summed by the same GEMMs."""
+    the first-order pass's factor rows, summed by the same GEMMs.  Returns None, with nothing launched, for
+    a head wider than the kernel takes (fp32 H > 268, fp64 H > 132)."""
     lib = nat.load()
     N, H = x.shape
     O = Q = H // 2
@@ -3121,6 +3147,8 @@ def eq_head_hvp(x, vec, params, gy, tx, tv, want_gy=True, want_w=True, factors_o
     rc = lib.tmdnet_eq_head_hvp(nat.dtype_code(x.dtype), N, H, nat.ptr(x), nat.ptr(vec), ws, nat.ptr(gy.contiguous()),
                                 nat.ptr(tx), nat.ptr(tv), nat.ptr(d_x), nat.ptr(d_vec), nat.ptr(d_gy), sv,
                                 nat.stream(x.device))
+    if rc == nat.UNSUPPORTED:  # wider than the HVP kernel's LDS takes: nothing was launched
+        return None
     nat.check(rc, "tmdnet_eq_head_hvp")
     if saves is None:
         return d_gy, d_x, d_vec, None
