@@ -143,18 +143,34 @@ int tmdnet_nl_backward_edges(int dtype, int n_atoms, const int32_t* neighbors, i
                              const void* grad_deltas, const void* grad_distances, const void* deltas,
                              const void* distances, void* grad_pos, void* stream);
 
-/* Second order of tmdnet_nl_backward (the double backward the reference gets by differentiating
- * NeighborAutograd::backward's index_add pair, neighbors_cuda.cu:43-71).  gg_pos [n][3] is the
- * cotangent of grad_pos.  Per edge e = (src -> dst) with w = gg[src]-gg[dst], u = delta/r:
- *   d_grad_deltas[e] = w,  d_grad_distances[e] = u.w  (0 when r == 0),
- *   d_pos[n] = sum_{e in row n} h[T[e]] - h[e],  h[e] = grad_distances[e]/r (w - u (u.w)).
- * grad_distances NULL = zero (d_pos = 0).  d_grad_deltas / d_grad_distances may be NULL (not
- * computed); when given, all max_pairs rows are written (padding slots 0).  Same list
- * requirements as tmdnet_nl_backward. */
+/* Second order of tmdnet_nl_backward and of tmdnet_nl_backward_virial (the double backward the reference gets
+ * by differentiating NeighborAutograd::backward's index_add pair, neighbors_cuda.cu:43-71), with the virial's
+ * cotangent as an optional operand.  With grad_distances the sum of both distance slots, the first-order pass
+ * gives
+ *   grad_pos[n] = sum_{e in row n} g[T[e]] - g[e],   out[m][a][b] = sum_{e: batch[dst] = m} g[e][a] * delta[e][b],
+ *   g[e] = grad_deltas[e] + u[e] * grad_distances[e],  u = delta/r.
+ * The cotangents are G = gg_pos [n][3] and B = g_virial [n_mol][3][3]; the scalar differentiated is
+ * S = <G, grad_pos> + <B, out>.  Per edge e = (src -> dst), m = batch[dst]:
+ *   w = (G[src] - G[dst]) + B_m delta,
+ *   d_grad_deltas[e] = w,   d_grad_distances[e] = u.w,
+ *   h[e] = dS/d delta[e] = grad_distances[e]/r (w - u (u.w)) + B_m^T g[e],
+ *   d_pos[n] = sum_{e in row n} h[T[e]] - h[e].
+ * Everything is 0 where r == 0 (self loops, padding); B_m = 0 where batch[dst] is outside [0, n_mol) (the
+ * first order skips those atoms).  Edges never cross molecules and delta[T[e]] = -delta[e] (image shift
+ * included), so w[T[e]] = -w[e] and one gather of G per edge serves both directions.
+ * grad_deltas, grad_distances and gg_pos may each be NULL (zero).  g_virial NULL (batch / n_mol then unused,
+ * grad_deltas not read) is the plain second order, w = G[src] - G[dst]: with gg_pos given it runs the kernel
+ * without the B terms (k_nl_backward2); g_virial all zeros gives the same bits from the other kernel
+ * (k_nl_backward2_virial: the shared terms in the same statement order, B_m read once per row).
+ * d_grad_deltas / d_grad_distances may be NULL (not computed); when given, all max_pairs rows are written
+ * (padding slots 0).  One row pass, 16 lanes per row, no atomics, deterministic; no molecule-count envelope
+ * (no LDS bins, unlike tmdnet_nl_backward_virial's sum pass).  Same list requirements as tmdnet_nl_backward,
+ * rows clamped to max_pairs. */
 int tmdnet_nl_backward2(int dtype, int n_atoms, const int32_t* row_ptr, const int32_t* src,
-                        const int32_t* transpose_map, int max_pairs, const void* grad_distances,
-                        const void* deltas, const void* distances, const void* gg_pos, void* d_pos,
-                        void* d_grad_deltas, void* d_grad_distances, void* stream);
+                        const int32_t* transpose_map, int max_pairs, const void* grad_deltas,
+                        const void* grad_distances, const void* deltas, const void* distances,
+                        const void* gg_pos, const int64_t* batch, int n_mol, const void* g_virial,
+                        void* d_pos, void* d_grad_deltas, void* d_grad_distances, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Edge geometry: radial basis + cosine cutoff + unit vectors, fused.  Replaces

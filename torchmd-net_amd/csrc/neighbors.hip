@@ -657,8 +657,93 @@ __global__ void k_nl_backward2(int n, const int* __restrict__ row_ptr, const int
   }
 }
 
+// k_nl_backward2 with a virial cotangent folded in (tmdnet_nl_backward2 given g_virial): the VJP of
+// k_nl_backward_virial's row pass, S = <gg, gpos> + <B, out> with out[m] = sum_{e into m} g_e (x) dl_e and
+// g_e = gd_e + u_e gr_e.  Per edge e = (s -> t), m = batch[t]:
+//   w = (gg[s] - gg[t]) + B_m dl,   d_gd[e] = w,   d_gr[e] = u.w,
+//   h[e] = gr/r (w - u (u.w)) + B_m^T g_e,   d_pos[n] = sum_{e in row n} h[T(e)] - h[e]   (all 0 when r == 0).
+// Edges stay inside a molecule and dl[T(e)] = -dl[e], so w(T(e)) = -w(e) as in k_nl_backward2; B_m^T g of
+// the transposed edge reads its own gd / gr.  B_m is loaded once per row (zero for a batch value outside
+// [0, n_mol)).  The shared terms keep k_nl_backward2's statements and order and the B terms are added after
+// them, so B = 0 reproduces its outputs bit for bit; gv NULL skips them.
+template <typename T>
+__global__ void k_nl_backward2_virial(int n, const int* __restrict__ row_ptr, const int32_t* __restrict__ src,
+                                      const int32_t* __restrict__ tr, int cap, const T* __restrict__ gd,
+                                      const T* __restrict__ gr, const T* __restrict__ dl,
+                                      const T* __restrict__ r, const T* __restrict__ gg,
+                                      const int64_t* __restrict__ batch, int n_mol, const T* __restrict__ gv,
+                                      T* __restrict__ dpos, T* __restrict__ dgd, T* __restrict__ dgr) {
+  const int gt = blockIdx.x * blockDim.x + threadIdx.x;
+  const int t = gt / kNlLanes, lane = gt % kNlLanes;
+  V3<T> acc{T(0), T(0), T(0)};
+  if (t < n) {
+    const int b = min(row_ptr[t], cap), e = min(row_ptr[t + 1], cap);
+    V3<T> gt3{T(0), T(0), T(0)};
+    if (gg) gt3 = {gg[3 * t + 0], gg[3 * t + 1], gg[3 * t + 2]};
+    T B[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) B[c] = T(0);
+    if (gv) {
+      const int64_t m = batch[t];
+      if (m >= 0 && m < n_mol) {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) B[c] = gv[(size_t)9 * m + c];
+      }
+    }
+    for (int k = b + lane; k < e; k += kNlLanes) {
+      const int s = src[k];
+      TMD_DCHECK(s >= 0 && s < n);
+      V3<T> w{T(0), T(0), T(0)};
+      if (gg) w = {gg[3 * s + 0] - gt3.x, gg[3 * s + 1] - gt3.y, gg[3 * s + 2] - gt3.z};
+      const bool live = r[k] != T(0);
+      if (gv && live) {
+        const T dx = dl[3 * k + 0], dy = dl[3 * k + 1], dz = dl[3 * k + 2];
+        w.x += B[0] * dx + B[1] * dy + B[2] * dz;
+        w.y += B[3] * dx + B[4] * dy + B[5] * dz;
+        w.z += B[6] * dx + B[7] * dy + B[8] * dz;
+      }
+      T uw;
+      const V3<T> dm = edge_grad2(k, w, gr, dl, r, uw);
+      acc.x -= dm.x; acc.y -= dm.y; acc.z -= dm.z;
+      if (gv) {
+        const V3<T> g = edge_grad(k, gd, gr, (const T*)nullptr, dl, r);
+        acc.x -= B[0] * g.x + B[3] * g.y + B[6] * g.z;
+        acc.y -= B[1] * g.x + B[4] * g.y + B[7] * g.z;
+        acc.z -= B[2] * g.x + B[5] * g.y + B[8] * g.z;
+      }
+      if (dgd) {
+        dgd[3 * k + 0] = live ? w.x : T(0);
+        dgd[3 * k + 1] = live ? w.y : T(0);
+        dgd[3 * k + 2] = live ? w.z : T(0);
+      }
+      if (dgr) dgr[k] = uw;
+      const int k2 = tr[k];
+      TMD_DCHECK(k2 >= -1 && k2 < cap);
+      if (k2 >= 0) {
+        T uw2;
+        const V3<T> dp = edge_grad2(k2, V3<T>{-w.x, -w.y, -w.z}, gr, dl, r, uw2);
+        acc.x += dp.x; acc.y += dp.y; acc.z += dp.z;
+        if (gv) {
+          const V3<T> g = edge_grad(k2, gd, gr, (const T*)nullptr, dl, r);
+          acc.x += B[0] * g.x + B[3] * g.y + B[6] * g.z;
+          acc.y += B[1] * g.x + B[4] * g.y + B[7] * g.z;
+          acc.z += B[2] * g.x + B[5] * g.y + B[8] * g.z;
+        }
+      }
+    }
+  }
+  acc.x = group_sum16(acc.x);
+  acc.y = group_sum16(acc.y);
+  acc.z = group_sum16(acc.z);
+  if (t < n && lane == 0) {
+    dpos[3 * t + 0] = acc.x;
+    dpos[3 * t + 1] = acc.y;
+    dpos[3 * t + 2] = acc.z;
+  }
+}
+
 // ---------------------------------------------------------------- host side
-#define TMD_CHECK(x)                               \
+#define TMD_CHECK(x)                            \
   do {                                             \
     if ((x) != hipSuccess) return kLaunchFailed;   \
   } while (0)
@@ -934,33 +1019,45 @@ extern "C" int tmdnet_nl_backward_virial(int dtype, int n_atoms, const int32_t* 
   return kUnsupported;
 }
 
-extern "C" int tmdnet_nl_backward2(int dtype, int n_atoms, const int32_t* row_ptr, const int32_t* src,
-                                   const int32_t* transpose_map, int max_pairs,
-                                   const void* grad_distances, const void* deltas,
-                                   const void* distances, const void* gg_pos, void* d_pos,
-                                   void* d_grad_deltas, void* d_grad_distances, void* stream) {
-  if (n_atoms <= 0 || max_pairs < 0 || !row_ptr || !src || !transpose_map || !gg_pos || !d_pos)
-    return kBadArgument;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t es = dtype == TMDNET_F64 ? 8 : 4;
+template <typename T>
+static int nl_backward2(int n_atoms, const int32_t* row_ptr, const int32_t* src, const int32_t* transpose_map,
+                        int max_pairs, const void* grad_deltas, const void* grad_distances, const void* deltas,
+                        const void* distances, const void* gg_pos, const int64_t* batch, int n_mol,
+                        const void* g_virial, void* d_pos, void* d_grad_deltas, void* d_grad_distances,
+                        hipStream_t st) {
   // padding slots belong to no CSR row: their gradients are zero
-  if (d_grad_deltas) TMD_CHECK(hipMemsetAsync(d_grad_deltas, 0, es * 3 * (size_t)max_pairs, st));
-  if (d_grad_distances) TMD_CHECK(hipMemsetAsync(d_grad_distances, 0, es * (size_t)max_pairs, st));
+  if (d_grad_deltas) TMD_CHECK(hipMemsetAsync(d_grad_deltas, 0, sizeof(T) * 3 * (size_t)max_pairs, st));
+  if (d_grad_distances) TMD_CHECK(hipMemsetAsync(d_grad_distances, 0, sizeof(T) * (size_t)max_pairs, st));
   const int tb = 256;
   dim3 g((unsigned)(((size_t)n_atoms * nl::kNlLanes + tb - 1) / tb));
-  if (dtype == TMDNET_F32)
-    hipLaunchKernelGGL(nl::k_nl_backward2<float>, g, dim3(tb), 0, st, n_atoms, row_ptr, src, transpose_map,
-                       max_pairs, (const float*)grad_distances, (const float*)deltas,
-                       (const float*)distances, (const float*)gg_pos, (float*)d_pos,
-                       (float*)d_grad_deltas, (float*)d_grad_distances);
-  else if (dtype == TMDNET_F64)
-    hipLaunchKernelGGL(nl::k_nl_backward2<double>, g, dim3(tb), 0, st, n_atoms, row_ptr, src, transpose_map,
-                       max_pairs, (const double*)grad_distances, (const double*)deltas,
-                       (const double*)distances, (const double*)gg_pos, (double*)d_pos,
-                       (double*)d_grad_deltas, (double*)d_grad_distances);
+  if (!g_virial && gg_pos)  // no virial cotangent: the plain second order
+    hipLaunchKernelGGL(nl::k_nl_backward2<T>, g, dim3(tb), 0, st, n_atoms, row_ptr, src, transpose_map, max_pairs,
+                       (const T*)grad_distances, (const T*)deltas, (const T*)distances, (const T*)gg_pos,
+                       (T*)d_pos, (T*)d_grad_deltas, (T*)d_grad_distances);
   else
-    return kUnsupported;
+    hipLaunchKernelGGL(nl::k_nl_backward2_virial<T>, g, dim3(tb), 0, st, n_atoms, row_ptr, src, transpose_map,
+                       max_pairs, (const T*)grad_deltas, (const T*)grad_distances, (const T*)deltas,
+                       (const T*)distances, (const T*)gg_pos, batch, n_mol, (const T*)g_virial, (T*)d_pos,
+                       (T*)d_grad_deltas, (T*)d_grad_distances);
   return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
+}
+
+extern "C" int tmdnet_nl_backward2(int dtype, int n_atoms, const int32_t* row_ptr, const int32_t* src,
+                                   const int32_t* transpose_map, int max_pairs, const void* grad_deltas,
+                                   const void* grad_distances, const void* deltas, const void* distances,
+                                   const void* gg_pos, const int64_t* batch, int n_mol, const void* g_virial,
+                                   void* d_pos, void* d_grad_deltas, void* d_grad_distances, void* stream) {
+  if (n_atoms <= 0 || max_pairs < 0 || !row_ptr || !src || !transpose_map || !deltas || !distances || !d_pos ||
+      (g_virial && (!batch || n_mol <= 0)))
+    return kBadArgument;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == TMDNET_F32)
+    return nl_backward2<float>(n_atoms, row_ptr, src, transpose_map, max_pairs, grad_deltas, grad_distances, deltas,
+                               distances, gg_pos, batch, n_mol, g_virial, d_pos, d_grad_deltas, d_grad_distances, st);
+  if (dtype == TMDNET_F64)
+    return nl_backward2<double>(n_atoms, row_ptr, src, transpose_map, max_pairs, grad_deltas, grad_distances, deltas,
+                                distances, gg_pos, batch, n_mol, g_virial, d_pos, d_grad_deltas, d_grad_distances, st);
+  return kUnsupported;
 }
 
 // ---------------------------------------------------------------- backward over a plain edge list

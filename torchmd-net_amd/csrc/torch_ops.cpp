@@ -314,8 +314,8 @@ struct NlGeomBwd2 : public Function<NlGeomBwd2> {
     Tensor d_gr = gr.defined() ? at::empty({cap}, opts(pos)) : Tensor();
     Tensor ggc = gg.contiguous();
     check(tmdnet_nl_backward2(dcode(pos), g.n(), ptr<int32_t>(row_ptr), ptr<int32_t>(src), ptr<int32_t>(tr), cap,
-                              ptr(gr), ptr(dl), ptr(dist), ptr(ggc), ptr(d_pos), ptr(d_gd), ptr(d_gr),
-                              stream_of(pos)),
+                              nullptr, ptr(gr), ptr(dl), ptr(dist), ptr(ggc), nullptr, 0, nullptr,  // no virial cotangent
+                              ptr(d_pos), ptr(d_gd), ptr(d_gr), stream_of(pos)),
           "tmdnet_nl_backward2");
     keep_graph(ctx, g);
     ctx->save_for_backward({pos, ggc, gr, dl, dist});

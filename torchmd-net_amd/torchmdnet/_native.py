@@ -43,7 +43,7 @@ SIGNATURES = {
                                         P]),
     "tmdnet_nl_backward": (I, [I, I, P, P, I, P, P, P, P, P, P, P]),
     "tmdnet_nl_backward_virial": (I, [I, I, P, P, I, P, P, P, P, P, P, P, I, P, P, P]),
-    "tmdnet_nl_backward2": (I, [I, I, P, P, P, I, P, P, P, P, P, P, P, P]),
+    "tmdnet_nl_backward2": (I, [I, I, P, P, P, I, P, P, P, P, P, P, I, P, P, P, P, P]),
     "tmdnet_nl_backward_edges": (I, [I, I, P, I, P, P, P, P, P, P]),
     "tmdnet_edge_geom_fwd": (I, [I, I, I, I, P, P, P, P, P, P, D, D, P, P, P, P, I, P, P, P]),
     "tmdnet_edge_geom_bwd": (I, [I, I, I, I, P, P, P, P, P, P, D, D, P, P, P, P, P, P, P, P, P, P]),

@@ -248,6 +248,13 @@ class _NeighborGeom(Function):
             g_dist, g_dist2 = g_dist2, None
         if g_deltas is None and g_dist is None:
             return None, None, None, None
+        sink = getattr(ctx.graph, "virial_sink", None)
+        if sink is not None and sink.open and sink.differentiable:
+            # energy_forces_virial(create_graph=True): the virial is an output of the force pass's Function
+            gpos, w = _NeighborGeomBwdVirial.apply(pos, g_deltas, g_dist, deltas, distances, ctx.graph, g_dist2,
+                                                   sink.batch, sink.n_mol)
+            sink.parts.append(w)
+            return gpos, None, None, None
         gpos = _NeighborGeomBwd.apply(pos, g_deltas, g_dist, deltas, distances, ctx.graph, g_dist2)
         return gpos, None, None, None
 
@@ -259,17 +266,29 @@ class VirialSink:
     pass of each such graph adds its share, and ``close`` -- when the public call returns -- ends it: a
     later backward over the same graph (a retained graph, a force-matching loss) finds it closed and leaves
     ``out`` alone.  The sink rides on the graph object, not on a thread-local: autograd runs the force pass
-    of GPU tensors on its device thread, not on the caller's."""
-    __slots__ = ("n_mol", "batch", "out", "open", "attached")
+    of GPU tensors on its device thread, not on the caller's.
 
-    def __init__(self, n_mol, batch, out):
+    ``differentiable`` (energy_forces_virial(create_graph=True)): nothing is added in place.  The force pass of
+    each graph runs as ``_NeighborGeomBwdVirial``, whose second output is that graph's virial, and leaves it
+    in ``parts``; ``total`` sums them out of place, so the result carries a ``grad_fn`` and a loss on it
+    reaches the second order (tmdnet_nl_backward2 with the virial's cotangent)."""
+    __slots__ = ("n_mol", "batch", "out", "open", "attached", "differentiable", "parts")
+
+    def __init__(self, n_mol, batch, out, differentiable=False):
         self.n_mol, self.batch, self.out = int(n_mol), batch, out
         self.open = True
         self.attached = 0
+        self.differentiable = bool(differentiable)
+        self.parts = []
+
+    def total(self):
+        """The differentiable mode's virial: the sum of the graphs' shares (``out``, zeros, when there is none)."""
+        return _sum_opt(self.parts) if self.parts else self.out
 
     def close(self):
         self.open = False
         self.batch = self.out = None  # the graphs that still hold the sink keep no tensor alive through it
+        self.parts = []
 
 
 _VIRIAL_SINK = None  # the open sink of the evaluation being recorded (read by build_graph only)
@@ -279,9 +298,9 @@ class virial_sink:
     """``with virial_sink(n_mol, batch, dtype) as sink:`` -- graphs built inside add their force pass's
     virial into ``sink.out`` (zeros [n_mol, 3, 3], allocated here; keep a reference before the block ends)."""
 
-    def __init__(self, n_mol, batch, dtype):
+    def __init__(self, n_mol, batch, dtype, differentiable=False):
         out = torch.zeros((int(n_mol), 3, 3), dtype=dtype, device=batch.device)
-        self.sink = VirialSink(n_mol, batch.contiguous(), out)
+        self.sink = VirialSink(n_mol, batch.contiguous(), out, differentiable)
 
     def __enter__(self):
         global _VIRIAL_SINK
@@ -442,9 +461,9 @@ class _NeighborGeomBwd2(Function):
         d_gr = torch.empty((cap,), dtype=pos.dtype, device=pos.device) if gr is not None else None
         gg = ggpos.contiguous()
         rc = lib.tmdnet_nl_backward2(nat.dtype_code(pos.dtype), n, nat.ptr(graph.row_ptr), nat.ptr(graph.src),
-                                     nat.ptr(graph.transpose), cap, nat.ptr(gr), nat.ptr(deltas),
-                                     nat.ptr(distances), nat.ptr(gg), nat.ptr(d_pos), nat.ptr(d_gd),
-                                     nat.ptr(d_gr), nat.stream(pos.device))
+                                     nat.ptr(graph.transpose), cap, None, nat.ptr(gr), nat.ptr(deltas),
+                                     nat.ptr(distances), nat.ptr(gg), None, 0, None,  # no virial cotangent
+                                     nat.ptr(d_pos), nat.ptr(d_gd), nat.ptr(d_gr), nat.stream(pos.device))
         nat.check(rc, "tmdnet_nl_backward2")
         ctx.graph = graph
         ctx.has = (gd is not None, gr is not None)
@@ -466,6 +485,132 @@ class _NeighborGeomBwd2(Function):
                                         create_graph=True, allow_unused=True)
         d_gr = grads[2] if r_ is not None else None
         return grads[0], grads[1], None, d_gr, None, None, None
+
+
+def nl_backward2_virial_composite(pos, ggpos, g_virial, gd, gr, deltas, distances, src, dst, batch, n_mol):
+    """Differentiable restatement of tmdnet_nl_backward2 with the virial's cotangent (the CPU yardstick and the
+    third-order path): (d_pos, d_gd, d_gr) = the gradient of <ggpos, nl_backward_composite(pos, gd, gr, ...)> +
+    <g_virial, nl_backward_virial_composite(gd, gr, None, ...)> w.r.t. (pos, gd, gr), ``gr`` being the sum of
+    both distance slots.  Per edge e = (s -> t), m = batch[t], u = dl / r, g = gd + u gr:
+    w = (ggpos[s] - ggpos[t]) + B_m dl,  d_gd = w,  d_gr = u.w,  h = gr / r (w - u (u.w)) + B_m^T g,
+    d_pos = index_add(s, h) - index_add(t, h).  Slots with r == 0 or an index outside the atoms (self loops,
+    padding -- whatever their other buffers hold) give zeros; B_m is zero where batch[t] is outside [0, n_mol).
+    Each of ggpos, g_virial, gd, gr may be None (zero)."""
+    n = pos.shape[0]
+    s, d = src.long().clamp(0, n - 1), dst.long().clamp(0, n - 1)
+    live = (distances != 0) & (src >= 0) & (src < n) & (dst >= 0) & (dst < n)
+    lv = live.unsqueeze(1)
+    raw = pos.index_select(0, s) - pos.index_select(0, d)
+    zero3 = torch.zeros_like(raw)
+    dl = torch.where(lv, raw + (deltas - raw).detach(), zero3)
+    r = torch.where(live, (dl * dl).sum(1), torch.ones_like(distances)).sqrt()
+    u = dl / r.unsqueeze(1)
+    gr_ = None if gr is None else torch.where(live, gr, torch.zeros_like(r))
+    g = zero3 if gd is None else torch.where(lv, gd, zero3)
+    if gr_ is not None:
+        g = g + u * gr_.unsqueeze(1)
+    w = zero3
+    if ggpos is not None:
+        w = torch.where(lv, ggpos.index_select(0, s) - ggpos.index_select(0, d), zero3)
+    Be = None
+    if g_virial is not None:
+        mol = batch.index_select(0, d)
+        inside = ((mol >= 0) & (mol < int(n_mol)) & live).to(pos.dtype).view(-1, 1, 1)
+        Be = g_virial.index_select(0, mol.clamp(0, max(int(n_mol) - 1, 0))) * inside
+        w = w + (Be * dl.unsqueeze(1)).sum(2)
+    uw = (u * w).sum(1, keepdim=True)
+    h = zero3
+    if gr_ is not None:
+        h = (gr_ / r).unsqueeze(1) * (w - u * uw)
+    if Be is not None:
+        h = h + (Be * g.unsqueeze(2)).sum(1)
+    d_pos = torch.zeros_like(pos).index_add(0, s, h).index_add(0, d, -h)
+    return d_pos, w, uw.squeeze(1)
+
+
+class _NeighborGeomBwd2Virial(Function):
+    """_NeighborGeomBwd2 with the virial's cotangent (HIP tmdnet_nl_backward2 given g_virial): the VJP of
+    _NeighborGeomBwdVirial's (gpos, w).  Its own backward (third order) differentiates the composite."""
+
+    @staticmethod
+    def forward(ctx, pos, ggpos, g_w, gd, gr, deltas, distances, graph, batch, n_mol):
+        lib = nat.load()
+        nat.require_gpu(pos, "nl_backward2_virial")
+        n = pos.shape[0]
+        cap = graph.n_edges
+        if deltas.shape != (cap, 3) or distances.shape != (cap,):
+            raise RuntimeError("nl_backward2_virial: deltas / distances do not match the graph's edge count")
+        gg = None if ggpos is None else ggpos.contiguous()
+        gw = None if g_w is None else g_w.to(pos.dtype).contiguous()
+        if gw is not None and gw.shape != (int(n_mol), 3, 3):
+            raise RuntimeError("nl_backward2_virial: the virial's cotangent is not [n_mol, 3, 3]")
+        for name, t, shape in (("gg_pos", gg, (n, 3)), ("grad_deltas", gd, (cap, 3)), ("grad_distances", gr, (cap,))):
+            if t is not None and (t.shape != shape or t.dtype != pos.dtype or not t.is_contiguous()):
+                raise RuntimeError(f"nl_backward2_virial: {name} does not match the graph")
+        if batch.dtype != torch.int64 or batch.shape != (n,) or not batch.is_contiguous():
+            raise RuntimeError('Expected "batch" to be a contiguous int64 vector matching "positions"')
+        deltas, distances = deltas.contiguous(), distances.contiguous()
+        d_pos = torch.empty_like(pos)
+        d_gd = torch.empty((cap, 3), dtype=pos.dtype, device=pos.device) if gd is not None else None
+        d_gr = torch.empty((cap,), dtype=pos.dtype, device=pos.device) if gr is not None else None
+        rc = lib.tmdnet_nl_backward2(nat.dtype_code(pos.dtype), n, nat.ptr(graph.row_ptr), nat.ptr(graph.src),
+                                     nat.ptr(graph.transpose), cap, nat.ptr(gd), nat.ptr(gr), nat.ptr(deltas),
+                                     nat.ptr(distances), nat.ptr(gg), nat.ptr(batch), int(n_mol), nat.ptr(gw),
+                                     nat.ptr(d_pos), nat.ptr(d_gd), nat.ptr(d_gr), nat.stream(pos.device))
+        nat.check(rc, "tmdnet_nl_backward2")
+        ctx.graph = graph
+        ctx.n_mol = int(n_mol)
+        ctx.save_for_backward(pos, gg, gw, gd, gr, deltas, distances, batch)
+        return d_pos, d_gd, d_gr
+
+    @staticmethod
+    def backward(ctx, g_dpos, g_dgd, g_dgr):
+        pos, gg, gw, gd, gr, deltas, distances, batch = ctx.saved_tensors
+        graph = ctx.graph
+        with torch.enable_grad():
+            leaf = lambda t: None if t is None else t.detach().requires_grad_(True)
+            p, g_, b_, d_, r_ = leaf(pos), leaf(gg), leaf(gw), leaf(gd), leaf(gr)
+            outs = nl_backward2_virial_composite(p, g_, b_, d_, r_, deltas, distances, graph.src, graph.dst,
+                                                 batch, ctx.n_mol)
+            pairs = [(o, go) for o, go in zip(outs, (g_dpos, g_dgd, g_dgr)) if go is not None and o.requires_grad]
+            ins = [t for t in (p, g_, b_, d_, r_) if t is not None]
+            grads = iter(torch.autograd.grad([o for o, _ in pairs], ins, [go for _, go in pairs],
+                                             create_graph=True, allow_unused=True)
+                         if pairs else [None] * len(ins))
+        take = lambda t: None if t is None else next(grads)
+        d_p, d_g, d_b, d_d, d_r = take(p), take(g_), take(b_), take(d_), take(r_)
+        return d_p, d_g, d_b, d_d, d_r, None, None, None, None, None
+
+
+class _NeighborGeomBwdVirial(Function):
+    """_NeighborGeomBwd for the differentiable virial: (gpos, w [n_mol, 3, 3]) of tmdnet_nl_backward_virial as
+    two outputs, so autograd sees the virial; backward receives (ggpos, g_w) -- either may be None -- and runs
+    the second order with both (tmdnet_nl_backward2)."""
+
+    @staticmethod
+    def forward(ctx, pos, g_deltas, g_dist, deltas, distances, graph, g_dist2, batch, n_mol):
+        gd = None if g_deltas is None else g_deltas.contiguous()
+        gr = None if g_dist is None else g_dist.contiguous()
+        gr2 = None if g_dist2 is None else g_dist2.contiguous()
+        gpos, w = nl_backward_virial(pos, gd, gr, gr2, deltas, distances, graph, batch, n_mol)
+        ctx.graph = graph
+        ctx.n_mol = int(n_mol)
+        ctx.two = gr2 is not None
+        ctx.set_materialize_grads(False)  # a loss on the virial alone sends no zero [N, 3] cotangent
+        ctx.save_for_backward(pos, gd, gr, gr2, deltas, distances, batch)
+        return gpos, w
+
+    @staticmethod
+    def backward(ctx, ggpos, g_w):
+        pos, gd, gr, gr2, deltas, distances, batch = ctx.saved_tensors
+        if ggpos is None and g_w is None:
+            return (None,) * 9
+        gr = _sum_opt([gr, gr2])
+        d_pos, d_gd, d_gr = _NeighborGeomBwd2Virial.apply(pos, ggpos, g_w, gd, gr, deltas, distances, ctx.graph,
+                                                          batch, ctx.n_mol)
+        d_gr = d_gr if gr is not None else None
+        return (d_pos, (d_gd if gd is not None else None), d_gr, None, None, None,
+                (d_gr if ctx.two else None), None, None)
 
 
 class DeviceOverflow:

@@ -310,15 +310,22 @@ class TorchMD_Net(nn.Module):
     @torch.jit.unused
     def energy_forces_virial(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None,
                              q: Optional[Tensor] = None, s: Optional[Tensor] = None,
-                             extra_args: Optional[Dict[str, Tensor]] = None
+                             extra_args: Optional[Dict[str, Tensor]] = None, create_graph: bool = False
                              ) -> Tuple[Tensor, Optional[Tensor], Tensor]:
         """``forward`` plus the per-molecule virial: returns (y, neg_dy, virial) with (y, neg_dy) exactly
         ``forward``'s and ``virial[m][a][b] = -dE_m/d eps_ab`` ([n_mol, 3, 3]) for the homogeneous strain
         pos -> pos (I + eps)^T, box -> box (I + eps)^T; without a box that is sum_{i in m} F_i[a] pos_i[b].
         Stress = -virial / det(box).  The virial is summed inside the force pass's neighbour backward kernel
-        (tmdnet_nl_backward_virial) over the model's graph and each pair prior's; it is detached (no
-        gradient of the virial: stress labels cannot be trained on yet) and has the dtype of ``y``.  Eager
-        only: the scripted path and tmdnet::et_energy_forces produce no virial."""
+        (tmdnet_nl_backward_virial) over the model's graph and each pair prior's, and has the dtype of ``y``.
+        Eager only: the scripted path and tmdnet::et_energy_forces produce no virial.
+
+        ``create_graph=False`` (default): the virial is detached.  ``create_graph=True``: the same values, attached
+        to the autograd graph -- each graph's virial is an output of its force pass, and a loss on it reaches the
+        parameters and the positions through the neighbour op's second order with the virial's cotangent
+        (tmdnet_nl_backward2), so a potential can be fitted to stress labels (``training.LNNPStep(virial_weight=...)``).
+        The label convention is this docstring's: ``virial = -stress * det(box)``, row a and column b those of
+        eps_ab.  ``create_graph=True`` raises ValueError for a precision-16 (half-storage) model and under stream
+        capture (captured stress training is not supported)."""
         from .. import kernels
         from .utils import check_stream_capturing
         from .wrappers import BaseWrapper
@@ -329,6 +336,12 @@ class TorchMD_Net(nn.Module):
             raise ValueError(f"energy_forces_virial does not support a wrapped representation model "
                              f"({type(self.representation_model).__name__}): its atoms are not the caller's")
         nat_batch = torch.zeros_like(z) if batch is None else batch
+        if create_graph and self._half_storage:
+            raise ValueError("energy_forces_virial(create_graph=True) does not support a precision-16 model "
+                             "(float16 storage): train on stress labels in precision 32 or 64")
+        if create_graph and pos.is_cuda and check_stream_capturing():
+            raise ValueError("energy_forces_virial(create_graph=True) cannot run under stream capture: the "
+                             "differentiable virial is eager only")
         if pos.is_cuda and check_stream_capturing():
             n_mol = int(self.output_model.dim_size)  # frozen by the warm-up call: no host read in a capture
             if n_mol <= 0:
@@ -336,6 +349,15 @@ class TorchMD_Net(nn.Module):
         else:
             n_mol = int(nat_batch.max()) + 1 if nat_batch.numel() else 0
         cdtype = torch.float32 if self._half_storage else pos.dtype
+        if create_graph:
+            # the same forward and force pass as the default (the same values); a training step that will
+            # differentiate them declares it with et_stack.second_order_expected, as for a force loss
+            with kernels.virial_sink(n_mol, nat_batch, cdtype, differentiable=True) as sink:
+                y, neg_dy = self(z, pos, batch, q=q, s=s, extra_args=extra_args)
+                if sink.attached == 0:
+                    raise RuntimeError("energy_forces_virial: no neighbour graph was built by this evaluation")
+                virial = sink.total()
+            return y, neg_dy, virial.to(y.dtype)
         with kernels.virial_sink(n_mol, nat_batch, cdtype) as sink:
             virial = sink.out
             y, neg_dy = self(z, pos, batch, q=q, s=s, extra_args=extra_args)

@@ -249,10 +249,14 @@ class LNNPStep:
     """One optimisation step of the reference training objective on a batch of molecules."""
 
     def __init__(self, model, lr=4e-4, weight_decay=0.0, y_weight=1.0, neg_dy_weight=1.0,
-                 lr_warmup_steps=0, group=None):
+                 lr_warmup_steps=0, group=None, virial_weight=0.0):
         self.model = model
         self.y_weight = y_weight
         self.neg_dy_weight = neg_dy_weight
+        # stress labels: virial_weight * MSE(virial) with the prediction of energy_forces_virial(create_graph=True)
+        # (label [n_mol, 3, 3] = -stress * det(box), that method's convention).  Eager only, one box per batch:
+        # the captured trainers refuse it and per-sample boxes are not supported.
+        self.virial_weight = virial_weight
         self.lr = lr
         self.lr_warmup_steps = lr_warmup_steps
         broadcast_parameters(model, 0, group)
@@ -260,7 +264,9 @@ class LNNPStep:
         self.opt = _make_optimizer(self.reduce, lr, weight_decay)
         self.global_step = 0
 
-    def loss(self, z, pos, batch, y, neg_dy):
+    def loss(self, z, pos, batch, y, neg_dy, virial=None):
+        if self.virial_weight > 0:
+            return self._loss_with_virial(z, pos, batch, y, neg_dy, virial)
         # a force loss differentiates the force pass again: let the ET stack record for its hand second order
         with second_order_expected(self.neg_dy_weight > 0):
             pred, pred_neg_dy = self.model(z, pos, batch)
@@ -272,6 +278,25 @@ class LNNPStep:
             # both terms in one launch (and one for their backward): kernels.mse2
             return kernels.mse2(pred, y, pred_neg_dy, neg_dy, self.y_weight, self.neg_dy_weight)
         loss = 0.0
+        if self.y_weight > 0:
+            loss = loss + self.y_weight * F.mse_loss(pred, y)
+        if self.neg_dy_weight > 0 and pred_neg_dy is not None:
+            loss = loss + self.neg_dy_weight * F.mse_loss(pred_neg_dy, neg_dy)
+        return loss
+
+    def _loss_with_virial(self, z, pos, batch, y, neg_dy, virial):
+        """The loss with the stress term: the energy and force terms as in ``loss`` (plain mse_loss), plus
+        virial_weight * MSE(virial).  The virial term differentiates the force pass again, like a force loss."""
+        if virial is None:
+            raise ValueError("LNNPStep(virial_weight > 0) needs a virial label [n_mol, 3, 3]")
+        with second_order_expected(self.neg_dy_weight > 0 or self.virial_weight > 0):
+            pred, pred_neg_dy, pred_virial = self.model.energy_forces_virial(z, pos, batch, create_graph=True)
+        if virial.shape != pred_virial.shape:
+            raise ValueError(f"LNNPStep: the virial label has shape {tuple(virial.shape)}, the prediction "
+                             f"{tuple(pred_virial.shape)}")
+        if y.ndim == 1:  # reference module.py:147-148
+            y = y.unsqueeze(1)
+        loss = self.virial_weight * F.mse_loss(pred_virial, virial)
         if self.y_weight > 0:
             loss = loss + self.y_weight * F.mse_loss(pred, y)
         if self.neg_dy_weight > 0 and pred_neg_dy is not None:
@@ -291,9 +316,9 @@ class LNNPStep:
             for g in self.opt.param_groups:
                 g["lr"] = scale * self.lr
 
-    def step(self, z, pos, batch, y, neg_dy):
+    def step(self, z, pos, batch, y, neg_dy, virial=None):
         self.opt.zero_grad(set_to_none=False)  # zeroes the flat buffer's views in place
-        loss = self.loss(z, pos, batch, y, neg_dy)
+        loss = self.loss(z, pos, batch, y, neg_dy, virial)
         self.backward(loss)
         self._warmup_lr()
         step_reduce(self.reduce, self.opt)
@@ -320,6 +345,9 @@ class GraphedTrainStep(LNNPStep):
     def __init__(self, model, z, pos, batch, y, neg_dy, margin=1.25, warmup=3, **kw):
         import math
         from .graphs import _distance_modules, refuse_pair_priors
+        if kw.get("virial_weight", 0.0) > 0:
+            raise ValueError("GraphedTrainStep does not support virial_weight > 0: the differentiable virial is "
+                             "eager only (use LNNPStep)")
         refuse_pair_priors(model)
         super().__init__(model, **kw)
         self.z, self.batch = z.clone(), batch.clone()
@@ -605,8 +633,12 @@ class PaddedGraphedTrainer:
     every batch is applied once, in order, as in the eager loop."""
 
     def __init__(self, model, batches, lr=4e-4, weight_decay=0.0, y_weight=1.0, neg_dy_weight=1.0,
-                 ema_alpha_y=1.0, ema_alpha_neg_dy=1.0, lr_warmup_steps=0, margin=1.3, warmup=2, group=None):
+                 ema_alpha_y=1.0, ema_alpha_neg_dy=1.0, lr_warmup_steps=0, margin=1.3, warmup=2, group=None,
+                 virial_weight=0.0):
         from .graphs import refuse_pair_priors
+        if virial_weight > 0:
+            raise ValueError("PaddedGraphedTrainer does not support virial_weight > 0: the differentiable virial "
+                             "is eager only (use LNNPStep)")
         refuse_pair_priors(model)
         self.model, self.batches = model, batches
         self.y_weight, self.neg_dy_weight = float(y_weight), float(neg_dy_weight)
