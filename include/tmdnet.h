@@ -82,6 +82,15 @@ enum { TMDNET_ACT_SILU = 0, TMDNET_ACT_SSP = 1, TMDNET_ACT_TANH = 2, TMDNET_ACT_
  * TMDNET_UNSUPPORTED.  Not periodic, the cell strategy needs a diagonal box (the caller supplies
  * 3*cutoff, as reference utils.py:199-202 does); a non-diagonal one is TMDNET_BAD_ARGUMENT.
  * tmdnet_nl_workspace_bytes sizes the cell arrays by the same rule from box9.
+ * use_periodic: 0 = no box; 1 = the one host box in box9 (above); k >= 2 = per-molecule boxes: box9 is then
+ * a DEVICE pointer to k - 1 boxes, [k - 1][9] doubles, row-major a, b, c each, in the same reduced triclinic
+ * form, and every atom of molecule m = batch[t] is imaged in box m (all molecules periodic).  Each wave
+ * reads its destination's box once and converts it as the host box is converted, so a stack of equal
+ * boxes gives bitwise the single-box list.  The molecule index is clamped to [0, k - 2] before the array
+ * is indexed: a batch value outside it gives wrong pairs, never a read outside the array.  The host does
+ * not read or validate the boxes.  Brute and shared only: the cell strategy with k >= 2 is
+ * TMDNET_UNSUPPORTED; a NULL box9 with k >= 2 is TMDNET_BAD_ARGUMENT (nothing launched in either case).
+ * tmdnet_nl_workspace_bytes takes a host box9 (or NULL) as before: brute and shared size nothing by it.
  * Pair numbering (optional): pair_row [max_pairs] and pair_edge [n_pair_slots > 0] given together are filled
  * as tmdnet_pair_index fills them, with no extra launch (the canonical counts ride on the count pass, their
  * scan on the row scan, the numbers on the transpose pass).  It needs sorted rows and the reversed edges:

@@ -72,7 +72,21 @@ template <typename T> struct Params {
   int loop, transpose;
   const int* unsorted;  // brute/shared: k_segments' per-block descent flags (nonzero somewhere: unsorted)
   int n_unsorted;       // ... their count
+  const double* boxes;  // brute/shared, per-molecule boxes (k_pairs<.., MOLBOX>): [n_boxes][9] on the DEVICE
+  int n_boxes;          // ... their count (> 0); molecule m takes boxes[clamp(m, 0, n_boxes - 1)]
 };
+
+// The box of molecule `m` (wave-uniform: one wave serves one destination, and its candidates are its own
+// molecule's) from the device array, converted as the host path converts its one box ((T)box[i]).  The
+// index is clamped, so a batch value outside the boxes reads a box of the array, never past it, and is
+// made provably uniform (readfirstlane), so the six entries come through the scalar cache once per wave.
+template <typename T>
+__device__ __forceinline__ Tric<T> load_mol_box(const Params<T>& P, int64_t m) {
+  const int64_t last = (int64_t)P.n_boxes - 1;
+  const int mi = __builtin_amdgcn_readfirstlane((int)(m < 0 ? 0 : (m > last ? last : m)));
+  const double* b = P.boxes + (size_t)9 * mi;
+  return {(T)b[0], (T)b[3], (T)b[4], (T)b[6], (T)b[7], (T)b[8]};
+}
 
 // Directed edge s -> t (neighbors[0]=s, neighbors[1]=t): delta = pos[s] - pos[t] (minimum image).
 template <typename T>
@@ -133,7 +147,10 @@ __global__ __launch_bounds__(256) void k_segments(const int64_t* __restrict__ ba
 // One wave64 per destination; 64 candidates per iteration; ballot counts/compacts.
 // Count pass with `ccounts`: also the number of canonical sources (s >= t) per row -- the pair
 // numbering of the sorted rows (see k_transpose) needs nothing else.
-template <typename T, bool FILL>
+// MOLBOX: every molecule has its own periodic box (P.boxes); the destination's is fetched once, before
+// the candidate loop, and takes the place of P.box in the same Tric::apply.  The single-box
+// instantiations (MOLBOX false) are the statements they were.
+template <typename T, bool FILL, bool MOLBOX = false>
 __global__ __launch_bounds__(256) void k_pairs(Params<T> P, const int* __restrict__ seg,
                                                int* __restrict__ counts, const int* __restrict__ row_ptr,
                                                int cap, int32_t* __restrict__ nb, T* __restrict__ dlt,
@@ -147,6 +164,7 @@ __global__ __launch_bounds__(256) void k_pairs(Params<T> P, const int* __restric
   const int lo = all ? 0 : seg[2 * t], hi = all ? P.n : seg[2 * t + 1];
   const V3<T> pt = load3(P.pos, t);
   const int64_t bt = P.batch[t];
+  if (MOLBOX) P.box = load_mol_box(P, bt);
   int off = FILL ? row_ptr[t] : 0;
   int coff = 0;
   for (int base = lo; base < hi; base += TMD_WAVE) {
@@ -830,6 +848,14 @@ static int build(int strategy, const T* pos, const int64_t* batch, int n, const 
                  char* ws, size_t ws_bytes, int32_t* prow, int32_t* pedge, int slots, int32_t* pair_rows,
                  hipStream_t st) {
   if (n <= 0 || cap <= 0 || !(cu > 0)) return kBadArgument;
+  // periodic >= 2: `box` is a DEVICE array of periodic - 1 boxes, one per molecule (brute / shared only);
+  // the host never reads it
+  const int n_boxes = periodic >= 2 ? periodic - 1 : 0;
+  if (n_boxes && !box) return kBadArgument;
+  if (n_boxes && strategy == TMDNET_NL_CELL) return kUnsupported;
+  static const double kUnitBox[9] = {0};
+  const double* dev_boxes = n_boxes ? box : nullptr;
+  if (n_boxes) box = kUnitBox;  // nothing below reads a per-molecule box on the host
   if (prow && (!pedge || slots <= 0 || !tr || !transpose || strategy == TMDNET_NL_CELL)) return kBadArgument;
   const Layout Lo = layout(n, strategy, box, cu);
   if (ws_bytes < Lo.total) return kWorkspaceTooSmall;
@@ -850,7 +876,9 @@ static int build(int strategy, const T* pos, const int64_t* batch, int n, const 
   const bool tric = strategy == TMDNET_NL_CELL && periodic && box_skewed(box);
   if (strategy == TMDNET_NL_CELL && !periodic && box_skewed(box)) return kBadArgument;
   P.rect = strategy == TMDNET_NL_CELL && !tric;
-  if (periodic || strategy == TMDNET_NL_CELL) {
+  P.boxes = dev_boxes;
+  P.n_boxes = n_boxes;
+  if ((periodic && !n_boxes) || strategy == TMDNET_NL_CELL) {
     P.box = {(T)box[0], (T)box[3], (T)box[4], (T)box[6], (T)box[7], (T)box[8]};
     P.L = {(T)box[0], (T)box[4], (T)box[8]};
   }
@@ -908,11 +936,19 @@ static int build(int strategy, const T* pos, const int64_t* batch, int n, const 
     hipLaunchKernelGGL(k_segments, dim3((n + tb - 1) / tb), dim3(tb), 0, st, batch, n, flag, seg);
     const int wpb = tb / TMD_WAVE;
     const dim3 g((n + wpb - 1) / wpb);
-    hipLaunchKernelGGL((k_pairs<T, false>), g, dim3(tb), 0, st, P, seg, counts, row_ptr, cap, nb, dlt, dist, cc);
+    if (n_boxes)
+      hipLaunchKernelGGL((k_pairs<T, false, true>), g, dim3(tb), 0, st, P, seg, counts, row_ptr, cap, nb, dlt, dist,
+                         cc);
+    else
+      hipLaunchKernelGGL((k_pairs<T, false>), g, dim3(tb), 0, st, P, seg, counts, row_ptr, cap, nb, dlt, dist, cc);
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, counts, n, row_ptr, num_pairs, cc, pairp, cap,
                        slots, prow ? pair_rows : nullptr);
-    hipLaunchKernelGGL((k_pairs<T, true>), g, dim3(tb), 0, st, P, seg, counts, row_ptr, cap, nb, dlt, dist,
-                       nullptr);
+    if (n_boxes)
+      hipLaunchKernelGGL((k_pairs<T, true, true>), g, dim3(tb), 0, st, P, seg, counts, row_ptr, cap, nb, dlt, dist,
+                         nullptr);
+    else
+      hipLaunchKernelGGL((k_pairs<T, true>), g, dim3(tb), 0, st, P, seg, counts, row_ptr, cap, nb, dlt, dist,
+                         nullptr);
     if (tr || pad)
       hipLaunchKernelGGL((k_transpose<T, true>), dim3((max(cap, prow ? slots : 0) + tb - 1) / tb), dim3(tb), 0, st,
                          nb, row_ptr, cap, num_pairs, tr, pad, dlt, dist, PR);
@@ -942,6 +978,7 @@ extern "C" int tmdnet_nl_build(int dtype, int strategy, const void* pos, const i
   // no pairing: no pair operand at all; pairing: both maps and their capacity (nl::build checks the rest)
   if (pair_row ? (!pair_edge || n_pair_slots <= 0) : (pair_edge || num_pair_rows || n_pair_slots != 0))
     return kBadArgument;
+  if (use_periodic >= 2 && !box9) return kBadArgument;  // per-molecule boxes: a device array is required
   double unit[9] = {0};
   const double* box = box9 ? box9 : unit;
   hipStream_t st = (hipStream_t)stream;

@@ -142,14 +142,48 @@ Built nl_build(const std::string& strategy_in, const Tensor& pos, const Tensor& 
   if (st == TMDNET_NL_BRUTE && n >= 32768) st = TMDNET_NL_SHARED;  // reference neighbors_cuda.cu:81-83
   double box9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   bool have_box = false;
-  if ((use_periodic || st == TMDNET_NL_CELL) && box.defined() && box.numel() > 0) {
+  // per-molecule boxes (n_boxes, 3, 3): a float64 device array, use_periodic = n_boxes + 1 (tmdnet_nl_build);
+  // the nine checks per box and n_boxes > batch.max() on the device, one host read, before any launch
+  Tensor boxes;
+  if (use_periodic && box.defined() && box.dim() == 3) {
+    TORCH_CHECK(st != TMDNET_NL_CELL,
+                "per-molecule \"box_vectors\" (n_molecules, 3, 3) are built by the brute and shared strategies "
+                "only: the cell list takes one (3, 3) box");
+    TORCH_CHECK(box.size(0) > 0 && box.size(1) == 3 && box.size(2) == 3,
+                "Expected \"box_vectors\" to have shape (3, 3) or (n_molecules, 3, 3)");
+    TORCH_CHECK(box.device() == pos.device(), "Expected per-molecule \"box_vectors\" on the device of \"positions\"");
+    boxes = box.detach().to(at::kDouble).contiguous();
+    const double c2 = 2 * cu;
+    auto e = [&](int64_t i, int64_t j) { return boxes.select(1, i).select(1, j); };
+    Tensor ok = at::stack({e(0, 1) == 0, e(0, 2) == 0, e(1, 2) == 0, e(0, 0) >= c2, e(1, 1) >= c2, e(2, 2) >= c2,
+                           e(0, 0) >= 2 * e(1, 0), e(0, 0) >= 2 * e(2, 0), e(1, 1) >= 2 * e(2, 1)},
+                          1);
+    Tensor bad = ok.logical_not();
+    Tensor bad_box = bad.any(1);
+    Tensor first = bad_box.to(at::kLong).argmax();
+    Tensor which = bad.index_select(0, first.reshape({1})).reshape({9}).to(at::kLong).argmax();
+    Tensor res = at::stack({bad_box.any().to(at::kLong), first, which, batch.max()}).to(at::kCPU);
+    const int64_t* r = res.data_ptr<int64_t>();
+    static const char* const kMsg[9] = {"box_vectors[0][1] != 0",
+                                        "box_vectors[0][2] != 0",
+                                        "box_vectors[1][2] != 0",
+                                        "box_vectors[0][0] < 2*cutoff",
+                                        "box_vectors[1][1] < 2*cutoff",
+                                        "box_vectors[2][2] < 2*cutoff",
+                                        "box_vectors[0][0] < 2*box_vectors[1][0]",
+                                        "box_vectors[0][0] < 2*box_vectors[1][0]",
+                                        "box_vectors[1][1] < 2*box_vectors[2][1]"};
+    TORCH_CHECK(!r[0], "molecule ", r[1], ": Invalid box vectors: ", kMsg[r[2]]);
+    TORCH_CHECK(r[3] < boxes.size(0), "Expected one box per molecule: \"box_vectors\" has ", boxes.size(0),
+                " boxes, \"batch\" reaches molecule ", r[3]);
+  } else if ((use_periodic || st == TMDNET_NL_CELL) && box.defined() && box.numel() > 0) {
     TORCH_CHECK(box.dim() == 2 && box.size(0) == 3 && box.size(1) == 3,
                 "Expected \"box_vectors\" to have shape (3, 3)");
     Tensor b = box.detach().to(at::kCPU).to(at::kDouble).contiguous();
     for (int i = 0; i < 9; ++i) box9[i] = b.data_ptr<double>()[i];
     have_box = true;
   }
-  if (use_periodic) {
+  if (use_periodic && !boxes.defined()) {
     TORCH_CHECK(have_box, "Expected \"box_vectors\" to have shape (3, 3)");
     validate_box(box9, cu);
   }
@@ -171,7 +205,9 @@ Built nl_build(const std::string& strategy_in, const Tensor& pos, const Tensor& 
   B.num = at::empty({1}, iopts(pos));
   if (want_csr) B.row_ptr = at::empty({n + 1}, iopts(pos));
   if (want_csr && include_transpose) B.tr = at::empty({cap}, iopts(pos));
-  check(tmdnet_nl_build(dcode(pos), st, pos.data_ptr(), batch.data_ptr<int64_t>(), n, bp, use_periodic ? 1 : 0, cl,
+  const double* build_box = boxes.defined() ? boxes.data_ptr<double>() : bp;
+  const int periodic_code = boxes.defined() ? static_cast<int>(boxes.size(0)) + 1 : (use_periodic ? 1 : 0);
+  check(tmdnet_nl_build(dcode(pos), st, pos.data_ptr(), batch.data_ptr<int64_t>(), n, build_box, periodic_code, cl,
                         cu, cap, loop ? 1 : 0, include_transpose ? 1 : 0, ptr<int32_t>(B.nb), ptr(B.dl),
                         ptr(B.dist), ptr<int32_t>(B.num), ptr<int32_t>(B.row_ptr), ptr<int32_t>(B.tr),
                         pad ? 1 : 0, ws.data_ptr(), static_cast<size_t>(ws.numel()), nullptr, nullptr, 0, nullptr,

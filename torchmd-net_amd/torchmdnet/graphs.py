@@ -11,6 +11,11 @@ whole forward + autograd force pass: ~600 launches become one graph launch.
     y, neg_dy = gm(pos_new)                              # copy-in + replay (same z/batch layout)
     gm.check_capacity()                                  # raises if a replay overflowed capacity
 
+``GraphedEnergyForces(..., box=boxes)`` captures a periodic evaluation whose cell can change between replays:
+the box -- ``(3, 3)`` or one per molecule ``(n_molecules, 3, 3)`` -- is kept as a static per-molecule device copy
+the captured neighbour build reads, and ``gm(pos_new, box=box_new)`` copies a new one into it before the replay
+(brute / shared strategies; no box is validated during a replay).
+
 ``GraphedEnergyForces(..., virial=True)`` also keeps the per-molecule virial of every replay in ``gm.virial``.
 
 Pair priors (ZBL, D2, Coulomb) build a neighbour list of their own: each gets its own static capacity from its
@@ -41,7 +46,7 @@ def refuse_pair_priors(model):
 
 class GraphedEnergyForces:
     def __init__(self, model, z, pos, batch, edge_capacity=None, margin=1.25, warmup=3, prior_capacity=None,
-                 virial=False):
+                 virial=False, box=None):
         if not model.derivative:
             raise ValueError("GraphedEnergyForces captures TorchMD_Net(derivative=True)")
         rep = model.representation_model
@@ -54,12 +59,21 @@ class GraphedEnergyForces:
         self.z = z.clone()
         self.batch = batch.clone()
         self.pos = pos.detach().clone()
-        # eager warm-up: sizes the edge capacity and the molecule count
-        y, f = model(self.z, self.pos.clone(), self.batch)
+        # the static box the captured build reads: always one float64 box per molecule on the device (a
+        # (3, 3) box is repeated), so a replay follows whatever __call__ copies into it
+        self.box = None
+        kw = {}
+        if box is not None:
+            n_mol = int(self.batch.max()) + 1
+            b = box.detach().to(device=dev, dtype=torch.float64)
+            self.box = (b.expand(n_mol, 3, 3) if b.dim() == 2 else b).contiguous().clone()
+            kw = {"box": self.box}
+        # eager warm-up: sizes the edge capacity and the molecule count (and validates the boxes)
+        y, f = model(self.z, self.pos.clone(), self.batch, **kw)
         dists = _distance_modules(model)
         if edge_capacity is None:
             from .models.utils import OptimizedDistance  # noqa: F401
-            g = rep.distance.graph(self.pos, self.batch)
+            g = rep.distance.graph(self.pos, self.batch, self.box)
             edge_capacity = int(math.ceil(g.num_pairs * margin / 256.0) * 256)
         self.edge_capacity = int(edge_capacity)
         for d in dists:
@@ -79,7 +93,7 @@ class GraphedEnergyForces:
         s.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(s):
             for _ in range(warmup):  # the captured call itself, so every kernel it launches has run once
-                (model.energy_forces_virial if virial else model)(self.z, self.pos, self.batch)
+                (model.energy_forces_virial if virial else model)(self.z, self.pos, self.batch, **kw)
         torch.cuda.current_stream(dev).wait_stream(s)
         torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
@@ -88,19 +102,24 @@ class GraphedEnergyForces:
         self.virial = None
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
             if virial:
-                self.y, self.neg_dy, self.virial = model.energy_forces_virial(self.z, self.pos, self.batch)
+                self.y, self.neg_dy, self.virial = model.energy_forces_virial(self.z, self.pos, self.batch, **kw)
             else:
-                self.y, self.neg_dy = model(self.z, self.pos, self.batch)
+                self.y, self.neg_dy = model(self.z, self.pos, self.batch, **kw)
         torch.cuda.synchronize(dev)
         # device flag written by every replay (lives in the graph's memory pool)
         self.overflow = rep.distance.last_overflow
         self.prior_overflows = [(type(p).__name__, p.last_overflow) for p in self.priors]
         self.dists = dists
 
-    def __call__(self, pos=None):
+    def __call__(self, pos=None, box=None):
         if pos is not None:
             with torch.no_grad():
                 self.pos.copy_(pos)
+        if box is not None:
+            if self.box is None:
+                raise ValueError("GraphedEnergyForces was captured without a box: pass box= at construction")
+            with torch.no_grad():
+                self.box.copy_(box)  # (3, 3) broadcasts over the molecules
         self.graph.replay()
         return self.y, self.neg_dy
 

@@ -182,7 +182,20 @@ def neighbor_pairs_raw(strategy, pos, batch, box, use_periodic, cutoff_lower, cu
     cap = int(max_pairs)
     dev = pos.device
     st = _STRATEGY[strategy]
-    box9 = _box9(box) if (use_periodic or st == nat.NL_CELL) else None
+    periodic_code = int(bool(use_periodic))
+    boxes = None
+    if use_periodic and box is not None and box.dim() == 3:
+        # per-molecule boxes: a device array, use_periodic = n_boxes + 1 (tmdnet_nl_build); never read here
+        if st == nat.NL_CELL:
+            raise RuntimeError(_MOLBOX_CELL_ERROR)
+        if box.shape[0] == 0 or box.shape[1:] != (3, 3):
+            raise RuntimeError('Expected "box_vectors" to have shape (3, 3) or (n_molecules, 3, 3)')
+        if box.device != dev:
+            raise RuntimeError('Expected per-molecule "box_vectors" on the device of "positions"')
+        boxes = box.detach().to(torch.float64).contiguous()
+        periodic_code = int(boxes.shape[0]) + 1
+        box = None
+    box9 = _box9(box) if ((use_periodic and boxes is None) or st == nat.NL_CELL) else None
     if st == nat.NL_CELL:
         if box9 is None:
             raise RuntimeError('Expected "box_size" to have shape (3, 3)')
@@ -199,7 +212,8 @@ def neighbor_pairs_raw(strategy, pos, batch, box, use_periodic, cutoff_lower, cu
     num = torch.empty((1,), dtype=torch.int32, device=dev)
     row_ptr = torch.empty((n + 1,), dtype=torch.int32, device=dev) if want_csr else None
     tr = torch.empty((cap,), dtype=torch.int32, device=dev) if (want_csr and include_transpose) else None
-    args = (nat.dtype_code(pos.dtype), st, nat.ptr(pos), nat.ptr(batch), n, box9, int(bool(use_periodic)),
+    args = (nat.dtype_code(pos.dtype), st, nat.ptr(pos), nat.ptr(batch), n,
+            box9 if boxes is None else nat.ptr(boxes), periodic_code,
             float(cutoff_lower), float(cutoff_upper), cap, int(bool(loop)), int(bool(include_transpose)),
             nat.ptr(nb), nat.ptr(dl), nat.ptr(dist), nat.ptr(num), nat.ptr(row_ptr), nat.ptr(tr),
             int(bool(pad_output)), nat.ptr(ws), int(ws.numel()))
@@ -227,6 +241,42 @@ def validate_box(box, cutoff_upper):
     for ok, msg in checks:
         if not ok:
             raise RuntimeError("Invalid box vectors: " + msg)
+
+
+_MOLBOX_CELL_ERROR = ('per-molecule "box_vectors" (n_molecules, 3, 3) are built by the brute and shared '
+                      'strategies only: the cell list takes one (3, 3) box')
+
+_BOX_CHECK_MESSAGES = ("box_vectors[0][1] != 0", "box_vectors[0][2] != 0", "box_vectors[1][2] != 0",
+                       "box_vectors[0][0] < 2*cutoff", "box_vectors[1][1] < 2*cutoff", "box_vectors[2][2] < 2*cutoff",
+                       "box_vectors[0][0] < 2*box_vectors[1][0]", "box_vectors[0][0] < 2*box_vectors[1][0]",
+                       "box_vectors[1][1] < 2*box_vectors[2][1]")
+
+
+def validate_boxes(boxes, cutoff_upper, batch=None):
+    """``validate_box`` for per-molecule boxes ``(n, 3, 3)``: the same nine checks on every box, evaluated on
+    the boxes' device and read back once.  The error is ``validate_box``'s for the first offending molecule,
+    prefixed with its index.  With ``batch`` the same read also carries ``batch.max()``: every molecule
+    needs a box (``n > batch.max()``)."""
+    if boxes.dim() != 3 or boxes.shape[0] == 0 or boxes.shape[1:] != (3, 3):
+        raise RuntimeError('Expected "box_vectors" to have shape (3, 3) or (n_molecules, 3, 3)')
+    v = boxes.detach().double()
+    c2 = 2 * float(cutoff_upper)
+    ok = torch.stack([v[:, 0, 1] == 0, v[:, 0, 2] == 0, v[:, 1, 2] == 0, v[:, 0, 0] >= c2, v[:, 1, 1] >= c2,
+                      v[:, 2, 2] >= c2, v[:, 0, 0] >= 2 * v[:, 1, 0], v[:, 0, 0] >= 2 * v[:, 2, 0],
+                      v[:, 1, 1] >= 2 * v[:, 2, 1]], dim=1)
+    bad = ~ok
+    bad_box = bad.any(dim=1)
+    first = bad_box.to(torch.int64).argmax()  # argmax of a 0/1 vector: its first 1
+    which = bad[first].to(torch.int64).argmax()
+    fields = [bad_box.any().to(torch.int64), first, which]
+    if batch is not None and batch.numel():
+        fields.append(batch.max().to(device=v.device, dtype=torch.int64))
+    res = torch.stack(fields).tolist()
+    if res[0]:
+        raise RuntimeError("molecule {}: Invalid box vectors: {}".format(res[1], _BOX_CHECK_MESSAGES[res[2]]))
+    if len(res) > 3 and res[3] >= boxes.shape[0]:
+        raise RuntimeError('Expected one box per molecule: "box_vectors" has {} boxes, "batch" reaches molecule {}'
+                           .format(boxes.shape[0], res[3]))
 
 
 class _NeighborGeom(Function):
@@ -635,7 +685,17 @@ def build_graph(pos, batch, cutoff_lower, cutoff_upper, max_num_pairs, loop=True
     ``pairs``: the pair numbering of ``pair_index`` is produced by the build itself (sorted-row
     strategies; the cell list numbers them lazily with tmdnet_pair_index)."""
     use_periodic = box is not None and box.numel() > 0
-    if use_periodic:
+    if use_periodic and box.dim() == 3:
+        # per-molecule boxes (n_boxes, 3, 3) on the device: brute / shared.  Eager: the nine checks per box
+        # and n_boxes > batch.max() in one host read, before anything is launched.  Static capacity: no host
+        # read at all -- the warm-up call checked the sizes and the kernel clamps the molecule index.
+        if strategy == "cell":
+            raise RuntimeError(_MOLBOX_CELL_ERROR)
+        if box.device != pos.device:
+            raise RuntimeError('Expected per-molecule "box_vectors" on the device of "positions"')
+        if static_capacity is None:
+            validate_boxes(box, cutoff_upper, batch)
+    elif use_periodic:
         validate_box(box, cutoff_upper)
     if strategy == "cell" and not use_periodic:
         lbox = float(cutoff_upper) * 3.0

@@ -95,11 +95,14 @@ class TorchMD_GN(nn.Module):
         raise RuntimeError(_SCRIPT_ERROR)
 
     def forward(self, z: Tensor, pos: Tensor, batch: Tensor, s: Optional[Tensor] = None,
-                q: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor], Tensor, Tensor, Tensor]:
+                q: Optional[Tensor] = None, box: Optional[Tensor] = None
+                ) -> Tuple[Tensor, Optional[Tensor], Tensor, Tensor, Tensor]:
+        """``box``: this call's periodic box, ``(3, 3)`` or one per molecule ``(n_molecules, 3, 3)``, handed to
+        ``self.distance.graph`` (``None``: the distance module's own box)."""
         if torch.jit.is_scripting():
             raise RuntimeError(_SCRIPT_ERROR)
         x = self.embedding(z)
-        graph = self.distance.graph(pos, batch)
+        graph = self.distance.graph(pos, batch) if box is None else self.distance.graph(pos, batch, box)
         de = self.distance_expansion
         if self.trainable_rbf and torch.is_grad_enabled():
             # trainable basis: parameters need gradients -> differentiable torch basis on the GPU

@@ -218,16 +218,29 @@ class OptimizedDistance(torch.nn.Module):
     def _max_pairs(self, n: int) -> int:
         return -self.max_num_pairs * n if self.max_num_pairs < 0 else self.max_num_pairs
 
-    def forward(self, pos: Tensor, batch: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+    def forward(self, pos: Tensor, batch: Optional[Tensor] = None,
+                box: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+        """``box``: a box for this call, ``(3, 3)`` or per molecule ``(n_molecules, 3, 3)`` (on the positions'
+        device; brute / shared); it wins over the constructor's.  ``None``: the constructor's box."""
         self.box = self.box.to(pos.dtype)
         max_pairs = self._max_pairs(pos.shape[0])
         if batch is None:
             batch = torch.zeros(pos.shape[0], dtype=torch.long, device=pos.device)
+        if box is not None:
+            edge_index, edge_vec, edge_weight, num_pairs = get_neighbor_pairs_kernel(
+                strategy=self.strategy, positions=pos, batch=batch, max_num_pairs=max_pairs,
+                cutoff_lower=self.cutoff_lower, cutoff_upper=self.cutoff_upper, loop=self.loop,
+                include_transpose=self.include_transpose, box_vectors=box, use_periodic=True)
+            return self._finish(edge_index, edge_vec, edge_weight, num_pairs, max_pairs)
         edge_index, edge_vec, edge_weight, num_pairs = get_neighbor_pairs_kernel(
             strategy=self.strategy, positions=pos, batch=batch, max_num_pairs=max_pairs,
             cutoff_lower=self.cutoff_lower, cutoff_upper=self.cutoff_upper, loop=self.loop,
             include_transpose=self.include_transpose, box_vectors=self.box,
             use_periodic=self.use_periodic)
+        return self._finish(edge_index, edge_vec, edge_weight, num_pairs, max_pairs)
+
+    def _finish(self, edge_index: Tensor, edge_vec: Tensor, edge_weight: Tensor, num_pairs: Tensor,
+                max_pairs: int) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
         if self.check_errors:
             if num_pairs[0] > max_pairs:
                 raise RuntimeError("Found num_pairs({}) > max_num_pairs({})".format(num_pairs[0], max_pairs))
@@ -242,16 +255,18 @@ class OptimizedDistance(torch.nn.Module):
             return edge_index, edge_weight, edge_vec
         return edge_index, edge_weight, None
 
-    def graph(self, pos: Tensor, batch: Optional[Tensor] = None):
-        """Symmetric CSR EdgeGraph (loop as configured) for the fused model kernels."""
+    def graph(self, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None):
+        """Symmetric CSR EdgeGraph (loop as configured) for the fused model kernels.  ``box`` as in
+        ``forward``: this call's box, ``(3, 3)`` or per molecule ``(n_molecules, 3, 3)``."""
         if not self.include_transpose:
             raise RuntimeError("the fused model path needs include_transpose=True")
         if batch is None:
             batch = torch.zeros(pos.shape[0], dtype=torch.long, device=pos.device)
-        box = self.box.to(pos.dtype) if self.use_periodic else None
         strategy = self.strategy
-        if strategy == "cell" and not self.use_periodic:
-            box = None
+        if box is None:
+            box = self.box.to(pos.dtype) if self.use_periodic else None
+            if strategy == "cell" and not self.use_periodic:
+                box = None
         g = kernels.build_graph(pos, batch, self.cutoff_lower, self.cutoff_upper,
                                 self._max_pairs(pos.shape[0]), loop=self.loop, strategy=strategy,
                                 box=box, check_errors=self.check_errors,

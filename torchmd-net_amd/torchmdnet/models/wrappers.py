@@ -38,8 +38,12 @@ class AtomFilter(BaseWrapper):
         self.remove_threshold = remove_threshold
 
     def forward(self, z: Tensor, pos: Tensor, batch: Tensor, q: Optional[Tensor] = None,
-                s: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor], Tensor, Tensor, Tensor]:
-        x, v, z, pos, batch = self.model(z, pos, batch=batch, q=q, s=s)
+                s: Optional[Tensor] = None, box: Optional[Tensor] = None
+                ) -> Tuple[Tensor, Optional[Tensor], Tensor, Tensor, Tensor]:
+        if box is None:
+            x, v, z, pos, batch = self.model(z, pos, batch=batch, q=q, s=s)
+        else:
+            x, v, z, pos, batch = self.model(z, pos, batch=batch, q=q, s=s, box=box)
 
         n_samples = len(batch.unique())
 

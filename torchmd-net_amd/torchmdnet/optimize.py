@@ -73,12 +73,13 @@ class TorchMD_GN_optimized(nn.Module):
         raise RuntimeError(_SCRIPT_ERROR)
 
     def forward(self, z: Tensor, pos: Tensor, batch: Tensor, s: Optional[Tensor] = None,
-                q: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor], Tensor, Tensor, Tensor]:
+                q: Optional[Tensor] = None, box: Optional[Tensor] = None
+                ) -> Tuple[Tensor, Optional[Tensor], Tensor, Tensor, Tensor]:
         if torch.jit.is_scripting():
             raise RuntimeError(_SCRIPT_ERROR)
         m = self.model
         x = m.embedding(z)
-        graph = m.distance.graph(pos, batch)
+        graph = m.distance.graph(pos, batch) if box is None else m.distance.graph(pos, batch, box)
         de = m.distance_expansion
         rbf_params = de.kernel_params()
         # the E x R basis rows only for the neighbour embedding

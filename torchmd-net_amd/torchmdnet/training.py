@@ -254,8 +254,9 @@ class LNNPStep:
         self.y_weight = y_weight
         self.neg_dy_weight = neg_dy_weight
         # stress labels: virial_weight * MSE(virial) with the prediction of energy_forces_virial(create_graph=True)
-        # (label [n_mol, 3, 3] = -stress * det(box), that method's convention).  Eager only, one box per batch:
-        # the captured trainers refuse it and per-sample boxes are not supported.
+        # (label [n_mol, 3, 3] = -stress * det(box), that method's convention).  Eager only: the captured
+        # trainers refuse it.  Structures with cells of their own pass ``box=`` [n_mol, 3, 3] to ``loss`` / ``step``
+        # (one box per molecule, TorchMD_Net.forward's argument); the captured trainers take no box.
         self.virial_weight = virial_weight
         self.lr = lr
         self.lr_warmup_steps = lr_warmup_steps
@@ -264,12 +265,15 @@ class LNNPStep:
         self.opt = _make_optimizer(self.reduce, lr, weight_decay)
         self.global_step = 0
 
-    def loss(self, z, pos, batch, y, neg_dy, virial=None):
+    def loss(self, z, pos, batch, y, neg_dy, virial=None, box=None):
+        """``box``: the batch's periodic box, ``(3, 3)`` or one per molecule ``(n_mol, 3, 3)``, passed to the model
+        (``None``: the model's own)."""
+        kw = {} if box is None else {"box": box}
         if self.virial_weight > 0:
-            return self._loss_with_virial(z, pos, batch, y, neg_dy, virial)
+            return self._loss_with_virial(z, pos, batch, y, neg_dy, virial, **kw)
         # a force loss differentiates the force pass again: let the ET stack record for its hand second order
         with second_order_expected(self.neg_dy_weight > 0):
-            pred, pred_neg_dy = self.model(z, pos, batch)
+            pred, pred_neg_dy = self.model(z, pos, batch, **kw)
         if y.ndim == 1:  # reference module.py:147-148
             y = y.unsqueeze(1)
         if (self.y_weight > 0 and self.neg_dy_weight > 0 and pred_neg_dy is not None and pred.is_cuda
@@ -284,13 +288,13 @@ class LNNPStep:
             loss = loss + self.neg_dy_weight * F.mse_loss(pred_neg_dy, neg_dy)
         return loss
 
-    def _loss_with_virial(self, z, pos, batch, y, neg_dy, virial):
+    def _loss_with_virial(self, z, pos, batch, y, neg_dy, virial, **kw):
         """The loss with the stress term: the energy and force terms as in ``loss`` (plain mse_loss), plus
         virial_weight * MSE(virial).  The virial term differentiates the force pass again, like a force loss."""
         if virial is None:
             raise ValueError("LNNPStep(virial_weight > 0) needs a virial label [n_mol, 3, 3]")
         with second_order_expected(self.neg_dy_weight > 0 or self.virial_weight > 0):
-            pred, pred_neg_dy, pred_virial = self.model.energy_forces_virial(z, pos, batch, create_graph=True)
+            pred, pred_neg_dy, pred_virial = self.model.energy_forces_virial(z, pos, batch, create_graph=True, **kw)
         if virial.shape != pred_virial.shape:
             raise ValueError(f"LNNPStep: the virial label has shape {tuple(virial.shape)}, the prediction "
                              f"{tuple(pred_virial.shape)}")
@@ -316,9 +320,10 @@ class LNNPStep:
             for g in self.opt.param_groups:
                 g["lr"] = scale * self.lr
 
-    def step(self, z, pos, batch, y, neg_dy, virial=None):
+    def step(self, z, pos, batch, y, neg_dy, virial=None, box=None):
         self.opt.zero_grad(set_to_none=False)  # zeroes the flat buffer's views in place
-        loss = self.loss(z, pos, batch, y, neg_dy, virial)
+        loss = self.loss(z, pos, batch, y, neg_dy, virial) if box is None else \
+            self.loss(z, pos, batch, y, neg_dy, virial, box=box)
         self.backward(loss)
         self._warmup_lr()
         step_reduce(self.reduce, self.opt)

@@ -29,6 +29,17 @@ class MissingEnergyException(Exception):
     pass
 
 
+def stress_from_virial(virial, box):
+    """Stress of every molecule from ``TorchMD_Net.energy_forces_virial``'s virial ``[n_mol, 3, 3]``
+    (``-dE_m/d eps``): ``-virial[m] / det(box_m)``, the inverse of the label convention
+    ``virial = -stress * det(box)``.  ``box``: ``(3, 3)`` (one cell for all) or ``(n_mol, 3, 3)``."""
+    b = box.to(device=virial.device, dtype=virial.dtype).reshape(-1, 3, 3)
+    vol = (b[:, 0, 0] * (b[:, 1, 1] * b[:, 2, 2] - b[:, 1, 2] * b[:, 2, 1])
+           - b[:, 0, 1] * (b[:, 1, 0] * b[:, 2, 2] - b[:, 1, 2] * b[:, 2, 0])
+           + b[:, 0, 2] * (b[:, 1, 0] * b[:, 2, 1] - b[:, 1, 1] * b[:, 2, 0]))
+    return -virial / vol.reshape(-1, 1, 1)
+
+
 def train_val_test_split(dset_len, train_size, val_size, test_size, seed, order=None):
     """Reference torchmdnet/utils.py:54-116: sizes as counts or fractions (one may be None = the
     rest), a seeded numpy permutation (``np.random.default_rng(seed)``), or a fixed ``order``."""
