@@ -88,9 +88,25 @@ enum { TMDNET_ACT_SILU = 0, TMDNET_ACT_SSP = 1, TMDNET_ACT_TANH = 2, TMDNET_ACT_
  * reads its destination's box once and converts it as the host box is converted, so a stack of equal
  * boxes gives bitwise the single-box list.  The molecule index is clamped to [0, k - 2] before the array
  * is indexed: a batch value outside it gives wrong pairs, never a read outside the array.  The host does
- * not read or validate the boxes.  Brute and shared only: the cell strategy with k >= 2 is
- * TMDNET_UNSUPPORTED; a NULL box9 with k >= 2 is TMDNET_BAD_ARGUMENT (nothing launched in either case).
+ * not read or validate the boxes.  Several boxes are brute and shared only: the cell strategy with k >= 3
+ * is TMDNET_UNSUPPORTED; a NULL box9 with k >= 2 is TMDNET_BAD_ARGUMENT (nothing launched in either case).
  * tmdnet_nl_workspace_bytes takes a host box9 (or NULL) as before: brute and shared size nothing by it.
+ * The cell strategy with use_periodic == 2 is the device-box cell build: box9 points to the ONE box, nine
+ * doubles on the device, which serves every molecule; the host does not read it.  A one-workgroup launch
+ * derives on the device what the host derives from a host box -- the cells per axis by the rule above in the
+ * same double arithmetic, the box converted to the dtype, whether it is skewed -- and leaves it in the
+ * workspace, where the binning and pair kernels read it; a diagonal and a skewed box take the same launches,
+ * so a box that becomes skewed between two builds (a captured constant-pressure run) needs nothing from the
+ * host.  For the same box the list is bitwise the host-box build's.  The cell capacity is what the workspace
+ * holds: pass tmdnet_nl_workspace_bytes(n_atoms, TMDNET_NL_CELL, bound9, cutoff) bytes, bound9 a HOST box that
+ * bounds the cells wanted, and the build may use up to that many cells (more with a larger workspace_bytes;
+ * fewer than 27: TMDNET_WORKSPACE_TOO_SMALL, nothing launched).  Nothing is refused on the device: an axis is
+ * clamped to 1024 cells, and a grid past the capacity is coarsened by taking cells off its largest axis, never
+ * below 3.  The list stays exact: a skewed box is binned in thicker fractional cells; a diagonal box keeps
+ * cutoff-wide cells and folds every atom past the last one into cell 0, which the first and the last cell
+ * both scan -- with room for few cells that build approaches all pairs.  A
+ * degenerate or non-finite device box gives a meaningless list, never an access outside a buffer.  The fill of
+ * the cell table and the sort's key width follow the capacity, not the grid.
  * Pair numbering (optional): pair_row [max_pairs] and pair_edge [n_pair_slots > 0] given together are filled
  * as tmdnet_pair_index fills them, with no extra launch (the canonical counts ride on the count pass, their
  * scan on the row scan, the numbers on the transpose pass).  It needs sorted rows and the reversed edges:

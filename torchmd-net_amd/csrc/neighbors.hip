@@ -21,6 +21,8 @@
 //    A periodic box with a skew entry (the reference's cell list refuses it) is binned in fractional
 //    coordinates along the lattice directions instead; its pairs are accepted with the triclinic
 //    minimum image of brute / shared, so the list holds brute's pairs with bitwise brute's deltas.
+//    The box of the cell strategy may live on the device (a captured run under a barostat): one small kernel
+//    then derives the grid there, into a record the binning and pair kernels read (k_cell_geom, DEVGEOM).
 //  * An optional transpose map T (T[e] = index of the reversed edge) lets the backward pass be a
 //    segmented CSR reduction with no atomics:  dpos[n] = sum_{e in row n} g[T(e)] - g[e].
 #include "common.h"
@@ -394,9 +396,73 @@ __device__ __forceinline__ void cell_of_tric(const CellGeom<T>& G, V3<T> p, int&
   cz = cell_frac(sz, G.nz);
 }
 
+// The geometry of a build whose box lives on the DEVICE (tmdnet_nl_build, cell strategy, use_periodic == 2):
+// what the host path passes by value -- the pair kernels' Params, the CellGeom and the choice of the TRIC
+// instantiation -- as a record in the workspace, written by k_cell_geom and read by the DEVGEOM forms of the
+// kernels below.
+template <typename T> struct CellRec {
+  Params<T> P;  // an image of the pair kernels' Params argument: box, L and rect are set, the rest is the launch's
+  CellGeom<T> G;
+  int tric;  // the box has a skew entry: cell_of_tric and Tric::apply; else cell_of and rect_apply
+};
+constexpr size_t kCellRecBytes = 512;  // its place in the workspace, whatever T
+static_assert(sizeof(CellRec<double>) <= kCellRecBytes && sizeof(CellRec<float>) <= kCellRecBytes, "");
+
+constexpr int kMaxCellsPerAxis = 1024;
+
+// One lane fills the record from the device box: the host's cell_dims in the same double arithmetic (every
+// operation rounded on its own, as the host compiler leaves them), the box converted to T as build() converts
+// the host box.  Where the host refuses, this clamps: an axis to kMaxCellsPerAxis cells, then the grid to
+// `cap_cells` (the cstart / cend entries the workspace holds, >= 27) by taking one cell off the largest axis
+// until it fits, never below 3.  The list stays exact: cell_of_tric's fractional cells get thicker than a cutoff;
+// cell_of keeps cutoff-wide cells and folds every index >= n into cell 0 (cell_axis), which cells 0 and n - 1 scan.
+// Any box value at all -- zero, infinite, NaN (every comparison below is false for it) -- leaves
+// 3 <= n_i <= kMaxCellsPerAxis and nx ny nz <= cap_cells: the keys of cell_axis / cell_frac then index inside
+// cstart / cend whatever the record's L, cut and box hold.
+template <typename T>
+__global__ __launch_bounds__(64) void k_cell_geom(const double* __restrict__ box, double cut, T cutT,
+                                                  int cap_cells, Params<T> P, CellRec<T>* __restrict__ rec) {
+#pragma clang fp contract(off)
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double b[9];
+  for (int i = 0; i < 9; ++i) b[i] = box[i];
+  const bool skew = b[3] != 0 || b[6] != 0 || b[7] != 0;
+  double w[3] = {b[0], b[4], b[8]};
+  if (skew) {
+    const double a0 = b[0], b0 = b[3], b1 = b[4], c0 = b[6], c1 = b[7], c2 = b[8];
+    const double bc[3] = {b1 * c2, -b0 * c2, b0 * c1 - b1 * c0};
+    w[0] = fabs(a0 * b1 * c2) / sqrt(bc[0] * bc[0] + bc[1] * bc[1] + bc[2] * bc[2]);
+    w[1] = fabs(b1 * c2) / sqrt(c1 * c1 + c2 * c2);
+    w[2] = fabs(c2);
+  }
+  int c[3];
+  for (int i = 0; i < 3; ++i) {
+    const double q = w[i] / cut;
+    c[i] = q >= 3 ? (q >= kMaxCellsPerAxis ? kMaxCellsPerAxis : (int)q) : 3;
+  }
+  while ((long long)c[0] * c[1] * c[2] > cap_cells) {  // ends at 3 x 3 x 3 = 27 <= cap_cells at the latest
+    const int i = c[0] >= c[1] ? (c[0] >= c[2] ? 0 : 2) : (c[1] >= c[2] ? 1 : 2);
+    if (c[i] <= 3) break;
+    --c[i];
+  }
+  CellRec<T> R{};
+  R.P = P;
+  R.G.L = {(T)b[0], (T)b[4], (T)b[8]};
+  R.G.cut = cutT;
+  R.G.nx = c[0];
+  R.G.ny = c[1];
+  R.G.nz = c[2];
+  R.G.box = {(T)b[0], (T)b[3], (T)b[4], (T)b[6], (T)b[7], (T)b[8]};
+  R.tric = skew ? 1 : 0;
+  R.P.box = R.G.box;
+  R.P.L = R.G.L;
+  R.P.rect = skew ? 0 : 1;
+  *rec = R;
+}
+
 template <typename T, bool TRIC>
-__global__ void k_cell_assign(const T* __restrict__ pos, int n, CellGeom<T> G, int* __restrict__ keys,
-                              int* __restrict__ vals) {
+__device__ __forceinline__ void cell_assign(const T* __restrict__ pos, int n, const CellGeom<T>& G,
+                                            int* __restrict__ keys, int* __restrict__ vals) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   int cx, cy, cz;
@@ -404,6 +470,24 @@ __global__ void k_cell_assign(const T* __restrict__ pos, int n, CellGeom<T> G, i
   else cell_of(G, load3(pos, i), cx, cy, cz);
   keys[i] = cx + G.nx * (cy + G.ny * cz);
   vals[i] = i;
+}
+
+// DEVGEOM: the geometry comes from the record behind `rec` (one address for the whole grid: scalar loads),
+// which also says which binning applies -- a wave-uniform branch between the two bodies the host-box forms
+// instantiate one of.  Each arm is the host form's body over the same values, not a merged restatement: the
+// compiler's choice of which multiply-subtract pairs it fuses follows the shape of the code around them, and
+// the device-box list has to equal the host-box list bit for bit in any box (see cell_pairs_outlined).  The host-box forms (DEVGEOM
+// false, rec unused) are the statements they were.
+template <typename T, bool TRIC, bool DEVGEOM = false>
+__global__ void k_cell_assign(const T* __restrict__ pos, int n, CellGeom<T> G, int* __restrict__ keys,
+                              int* __restrict__ vals, const CellRec<T>* __restrict__ rec) {
+  if (DEVGEOM) {
+    G = rec->G;
+    if (rec->tric) cell_assign<T, true>(pos, n, G, keys, vals);
+    else cell_assign<T, false>(pos, n, G, keys, vals);
+  } else {
+    cell_assign<T, TRIC>(pos, n, G, keys, vals);
+  }
 }
 
 __global__ void k_cell_bounds(const int* __restrict__ skeys, int n, int* __restrict__ cstart,
@@ -422,23 +506,19 @@ __global__ void k_cell_bounds(const int* __restrict__ skeys, int n, int* __restr
 // wraps with the triclinic image (P.rect == 0).  A source within the cutoff of t has every fractional
 // coordinate within cutoff / w_i <= 1 / n_i of t's (w_i the cell's perpendicular width), so it lies in
 // one of the 27 cells; with n_i == 3 the three offsets are the whole axis.  n_i >= 3 keeps the 27 distinct.
-template <typename T, bool FILL, bool TRIC>
-__global__ __launch_bounds__(256) void k_cell_pairs(Params<T> P, CellGeom<T> G,
-                                                    const int* __restrict__ skeys,
-                                                    const int* __restrict__ svals,
-                                                    const int* __restrict__ cstart,
-                                                    const int* __restrict__ cend,
-                                                    int* __restrict__ counts,
-                                                    const int* __restrict__ row_ptr, int cap,
-                                                    int32_t* __restrict__ nb, T* __restrict__ dlt,
-                                                    T* __restrict__ dist) {
+template <typename T, bool FILL>
+__device__ __forceinline__ void cell_pairs(const bool tric, const Params<T>& P, const CellGeom<T>& G,
+                                           const int* __restrict__ skeys, const int* __restrict__ svals,
+                                           const int* __restrict__ cstart, const int* __restrict__ cend,
+                                           int* __restrict__ counts, const int* __restrict__ row_ptr, int cap,
+                                           int32_t* __restrict__ nb, T* __restrict__ dlt, T* __restrict__ dist) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= P.n) return;
   const int t = svals[p];
   const V3<T> pt = load3(P.pos, t);
   const int64_t bt = P.batch[t];
   int cx, cy, cz;
-  if (TRIC) cell_of_tric(G, pt, cx, cy, cz);
+  if (tric) cell_of_tric(G, pt, cx, cy, cz);
   else cell_of(G, pt, cx, cy, cz);
   int off = FILL ? row_ptr[t] : 0;
   for (int k = 0; k < 27; ++k) {
@@ -469,6 +549,42 @@ __global__ __launch_bounds__(256) void k_cell_pairs(Params<T> P, CellGeom<T> G,
     }
   }
   if (!FILL) counts[t] = off;
+}
+
+// The body behind reference parameters, for the DEVGEOM form.  Not inlined on purpose: the image arithmetic of
+// accept() leaves the fusing of d -= round(k) * c to the compiler, and which of the products it fuses follows from
+// how the vectoriser lays out the box entries -- with a kernel argument (known dereferenceable) it loads b0, b1, c0
+// as one vector and fuses the b step, with plain loads from a record it fused the c step, one rounding apart
+// whenever round(k) * c is inexact.  Reference parameters carry the same guarantee as a kernel argument, and the
+// compiled arithmetic is the host form's (compared in the ISA; tests/test_gpu_cell_devbox.py pins the result:
+// device-box and host-box lists bit for bit in a box that fills the float32 mantissa, images 3 boxes away).
+template <typename T, bool FILL>
+__device__ __noinline__ void cell_pairs_outlined(const bool tric, const Params<T>& P, const CellGeom<T>& G,
+                                                 const int* __restrict__ skeys, const int* __restrict__ svals,
+                                                 const int* __restrict__ cstart, const int* __restrict__ cend,
+                                                 int* __restrict__ counts, const int* __restrict__ row_ptr, int cap,
+                                                 int32_t* __restrict__ nb, T* __restrict__ dlt, T* __restrict__ dist) {
+  cell_pairs<T, FILL>(tric, P, G, skeys, svals, cstart, cend, counts, row_ptr, cap, nb, dlt, dist);
+}
+
+// DEVGEOM: Params (with the minimum image's P.box / P.L / P.rect, which accept() reads), G and the binning choice
+// come from the record; the kernel's own P and G arguments are not read.
+template <typename T, bool FILL, bool TRIC, bool DEVGEOM = false>
+__global__ __launch_bounds__(256) void k_cell_pairs(Params<T> P, CellGeom<T> G,
+                                                    const int* __restrict__ skeys,
+                                                    const int* __restrict__ svals,
+                                                    const int* __restrict__ cstart,
+                                                    const int* __restrict__ cend,
+                                                    int* __restrict__ counts,
+                                                    const int* __restrict__ row_ptr, int cap,
+                                                    int32_t* __restrict__ nb, T* __restrict__ dlt,
+                                                    T* __restrict__ dist, const CellRec<T>* __restrict__ rec) {
+  if (DEVGEOM) {
+    cell_pairs_outlined<T, FILL>(rec->tric != 0, rec->P, rec->G, skeys, svals, cstart, cend, counts, row_ptr, cap, nb,
+                                 dlt, dist);
+  } else {
+    cell_pairs<T, FILL>(TRIC, P, G, skeys, svals, cstart, cend, counts, row_ptr, cap, nb, dlt, dist);
+  }
 }
 
 // ---------------------------------------------------------------- backward (segmented, no atomics)
@@ -810,7 +926,7 @@ static size_t cub_sort_bytes(int n) {
 }
 
 struct Layout {
-  size_t flag, seg, counts, rowp, cc, pairp, keys, vals, skeys, svals, cstart, cend, cub, total;
+  size_t flag, seg, counts, rowp, cc, pairp, keys, vals, skeys, svals, rec, cub, cstart, cend, total;
   size_t cub_bytes;
   int ncells;
 };
@@ -832,10 +948,13 @@ static Layout layout(int n, int strategy, const double* box, double cut) {
     L.vals = o; o += align16(sizeof(int) * (size_t)n);
     L.skeys = o; o += align16(sizeof(int) * (size_t)n);
     L.svals = o; o += align16(sizeof(int) * (size_t)n);
-    L.cstart = o; o += align16(sizeof(int) * (size_t)L.ncells);
-    L.cend = o; o += align16(sizeof(int) * (size_t)L.ncells);
+    L.rec = o; o += kCellRecBytes;  // the device-box build's CellRec
     L.cub_bytes = cub_sort_bytes(n);
     L.cub = o; o += align16(L.cub_bytes);
+    // cstart / cend last and back to back: a device-box build takes as many cells as the workspace it is
+    // handed holds behind L.cstart, sizeof(int) * 2 bytes each
+    L.cstart = o; o += sizeof(int) * (size_t)L.ncells;
+    L.cend = o; o += sizeof(int) * (size_t)L.ncells;
   }
   L.total = o;
   return L;
@@ -848,16 +967,26 @@ static int build(int strategy, const T* pos, const int64_t* batch, int n, const 
                  char* ws, size_t ws_bytes, int32_t* prow, int32_t* pedge, int slots, int32_t* pair_rows,
                  hipStream_t st) {
   if (n <= 0 || cap <= 0 || !(cu > 0)) return kBadArgument;
-  // periodic >= 2: `box` is a DEVICE array of periodic - 1 boxes, one per molecule (brute / shared only);
-  // the host never reads it
+  // periodic >= 2: `box` is a DEVICE array of periodic - 1 boxes, one per molecule (brute / shared), or the
+  // one box of the cell list (periodic == 2: the device-box cell build); the host never reads it
   const int n_boxes = periodic >= 2 ? periodic - 1 : 0;
   if (n_boxes && !box) return kBadArgument;
-  if (n_boxes && strategy == TMDNET_NL_CELL) return kUnsupported;
+  if (n_boxes > 1 && strategy == TMDNET_NL_CELL) return kUnsupported;
+  const bool devcell = n_boxes == 1 && strategy == TMDNET_NL_CELL;
   static const double kUnitBox[9] = {0};
   const double* dev_boxes = n_boxes ? box : nullptr;
   if (n_boxes) box = kUnitBox;  // nothing below reads a per-molecule box on the host
   if (prow && (!pedge || slots <= 0 || !tr || !transpose || strategy == TMDNET_NL_CELL)) return kBadArgument;
-  const Layout Lo = layout(n, strategy, box, cu);
+  Layout Lo = layout(n, strategy, box, cu);
+  if (devcell) {
+    // the cell capacity is what the workspace holds behind the fixed parts, not what a host box asks for
+    const size_t room = ws_bytes > Lo.cstart ? (ws_bytes - Lo.cstart) / (2 * sizeof(int)) : 0;
+    if (room < 27) return kWorkspaceTooSmall;
+    const size_t most = (size_t)kMaxCellsPerAxis * kMaxCellsPerAxis * kMaxCellsPerAxis;
+    Lo.ncells = (int)(room < most ? room : most);
+    Lo.cend = Lo.cstart + sizeof(int) * (size_t)Lo.ncells;
+    Lo.total = Lo.cend + sizeof(int) * (size_t)Lo.ncells;
+  }
   if (ws_bytes < Lo.total) return kWorkspaceTooSmall;
   int* flag = (int*)(ws + Lo.flag);
   int* seg = (int*)(ws + Lo.seg);
@@ -871,14 +1000,14 @@ static int build(int strategy, const T* pos, const int64_t* batch, int n, const 
   P.pos = pos;
   P.batch = batch;
   P.n = n;
-  P.periodic = periodic;
+  P.periodic = devcell ? 1 : periodic;
   // the cell list of a periodic skewed box: fractional-coordinate cells, the triclinic image of brute
   const bool tric = strategy == TMDNET_NL_CELL && periodic && box_skewed(box);
   if (strategy == TMDNET_NL_CELL && !periodic && box_skewed(box)) return kBadArgument;
   P.rect = strategy == TMDNET_NL_CELL && !tric;
-  P.boxes = dev_boxes;
-  P.n_boxes = n_boxes;
-  if ((periodic && !n_boxes) || strategy == TMDNET_NL_CELL) {
+  P.boxes = devcell ? nullptr : dev_boxes;
+  P.n_boxes = devcell ? 0 : n_boxes;
+  if ((periodic && !n_boxes) || (strategy == TMDNET_NL_CELL && !devcell)) {
     P.box = {(T)box[0], (T)box[3], (T)box[4], (T)box[6], (T)box[7], (T)box[8]};
     P.L = {(T)box[0], (T)box[4], (T)box[8]};
   }
@@ -890,19 +1019,26 @@ static int build(int strategy, const T* pos, const int64_t* batch, int n, const 
 
   const int tb = 256;
   if (strategy == TMDNET_NL_CELL) {
-    CellDims cd;
-    if (const int rc = cell_dims(box, cu, cd)) return rc;
+    CellDims cd{3, 3, 3};
+    if (!devcell)
+      if (const int rc = cell_dims(box, cu, cd)) return rc;
     CellGeom<T> G{{(T)box[0], (T)box[4], (T)box[8]}, cuT, cd.nx, cd.ny, cd.nz, P.box};
+    // device box: G above is a placeholder, the kernels take the record k_cell_geom leaves in the workspace
+    CellRec<T>* rec = devcell ? (CellRec<T>*)(ws + Lo.rec) : nullptr;
+    const dim3 ga((n + tb - 1) / tb), gb(tb);
     int* keys = (int*)(ws + Lo.keys);
     int* vals = (int*)(ws + Lo.vals);
     int* skeys = (int*)(ws + Lo.skeys);
     int* svals = (int*)(ws + Lo.svals);
     int* cstart = (int*)(ws + Lo.cstart);
     int* cend = (int*)(ws + Lo.cend);
-    if (tric)
-      hipLaunchKernelGGL((k_cell_assign<T, true>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, pos, n, G, keys, vals);
+    if (devcell) {
+      hipLaunchKernelGGL(k_cell_geom<T>, dim3(1), dim3(64), 0, st, dev_boxes, cu, cuT, Lo.ncells, P, rec);
+      hipLaunchKernelGGL((k_cell_assign<T, false, true>), ga, gb, 0, st, pos, n, G, keys, vals, rec);
+    } else if (tric)
+      hipLaunchKernelGGL((k_cell_assign<T, true>), ga, gb, 0, st, pos, n, G, keys, vals, rec);
     else
-      hipLaunchKernelGGL((k_cell_assign<T, false>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, pos, n, G, keys, vals);
+      hipLaunchKernelGGL((k_cell_assign<T, false>), ga, gb, 0, st, pos, n, G, keys, vals, rec);
     size_t cb = Lo.cub_bytes;
     int endbit = 1;
     while ((1 << endbit) < Lo.ncells && endbit < 31) ++endbit;
@@ -911,20 +1047,26 @@ static int build(int strategy, const T* pos, const int64_t* batch, int n, const 
       return kLaunchFailed;
     TMD_CHECK(hipMemsetAsync(cstart, 0xFF, sizeof(int) * (size_t)Lo.ncells, st));
     hipLaunchKernelGGL(k_cell_bounds, dim3((n + tb - 1) / tb), dim3(tb), 0, st, skeys, n, cstart, cend);
-    if (tric)
-      hipLaunchKernelGGL((k_cell_pairs<T, false, true>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, P, G, skeys,
-                         svals, cstart, cend, counts, row_ptr, cap, nb, dlt, dist);
+    if (devcell)
+      hipLaunchKernelGGL((k_cell_pairs<T, false, false, true>), ga, gb, 0, st, P, G, skeys, svals, cstart, cend,
+                         counts, row_ptr, cap, nb, dlt, dist, rec);
+    else if (tric)
+      hipLaunchKernelGGL((k_cell_pairs<T, false, true>), ga, gb, 0, st, P, G, skeys, svals, cstart, cend, counts,
+                         row_ptr, cap, nb, dlt, dist, rec);
     else
-      hipLaunchKernelGGL((k_cell_pairs<T, false, false>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, P, G, skeys,
-                         svals, cstart, cend, counts, row_ptr, cap, nb, dlt, dist);
+      hipLaunchKernelGGL((k_cell_pairs<T, false, false>), ga, gb, 0, st, P, G, skeys, svals, cstart, cend, counts,
+                         row_ptr, cap, nb, dlt, dist, rec);
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, counts, n, row_ptr, num_pairs, nullptr, nullptr,
                        cap, 0, nullptr);
-    if (tric)
-      hipLaunchKernelGGL((k_cell_pairs<T, true, true>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, P, G, skeys,
-                         svals, cstart, cend, counts, row_ptr, cap, nb, dlt, dist);
+    if (devcell)
+      hipLaunchKernelGGL((k_cell_pairs<T, true, false, true>), ga, gb, 0, st, P, G, skeys, svals, cstart, cend,
+                         counts, row_ptr, cap, nb, dlt, dist, rec);
+    else if (tric)
+      hipLaunchKernelGGL((k_cell_pairs<T, true, true>), ga, gb, 0, st, P, G, skeys, svals, cstart, cend, counts,
+                         row_ptr, cap, nb, dlt, dist, rec);
     else
-      hipLaunchKernelGGL((k_cell_pairs<T, true, false>), dim3((n + tb - 1) / tb), dim3(tb), 0, st, P, G, skeys,
-                         svals, cstart, cend, counts, row_ptr, cap, nb, dlt, dist);
+      hipLaunchKernelGGL((k_cell_pairs<T, true, false>), ga, gb, 0, st, P, G, skeys, svals, cstart, cend, counts,
+                         row_ptr, cap, nb, dlt, dist, rec);
     if (tr || pad)
       hipLaunchKernelGGL((k_transpose<T, false>), dim3((cap + tb - 1) / tb), dim3(tb), 0, st, nb, row_ptr, cap,
                          num_pairs, tr, pad, dlt, dist, PR);

@@ -143,12 +143,16 @@ Built nl_build(const std::string& strategy_in, const Tensor& pos, const Tensor& 
   double box9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   bool have_box = false;
   // per-molecule boxes (n_boxes, 3, 3): a float64 device array, use_periodic = n_boxes + 1 (tmdnet_nl_build);
-  // the nine checks per box and n_boxes > batch.max() on the device, one host read, before any launch
+  // the nine checks per box and n_boxes > batch.max() on the device, one host read, before any launch.
+  // The cell list takes one such box, (1, 3, 3), for every molecule (the device-box cell build): the same
+  // read brings the box back, and the workspace is sized for exactly that box.
   Tensor boxes;
+  bool cell_box = false;
   if (use_periodic && box.defined() && box.dim() == 3) {
-    TORCH_CHECK(st != TMDNET_NL_CELL,
+    TORCH_CHECK(st != TMDNET_NL_CELL || box.size(0) <= 1,
                 "per-molecule \"box_vectors\" (n_molecules, 3, 3) are built by the brute and shared strategies "
                 "only: the cell list takes one (3, 3) box");
+    cell_box = st == TMDNET_NL_CELL;
     TORCH_CHECK(box.size(0) > 0 && box.size(1) == 3 && box.size(2) == 3,
                 "Expected \"box_vectors\" to have shape (3, 3) or (n_molecules, 3, 3)");
     TORCH_CHECK(box.device() == pos.device(), "Expected per-molecule \"box_vectors\" on the device of \"positions\"");
@@ -162,8 +166,20 @@ Built nl_build(const std::string& strategy_in, const Tensor& pos, const Tensor& 
     Tensor bad_box = bad.any(1);
     Tensor first = bad_box.to(at::kLong).argmax();
     Tensor which = bad.index_select(0, first.reshape({1})).reshape({9}).to(at::kLong).argmax();
-    Tensor res = at::stack({bad_box.any().to(at::kLong), first, which, batch.max()}).to(at::kCPU);
-    const int64_t* r = res.data_ptr<int64_t>();
+    // one host read; the cell list's one box rides on it (as doubles, exact for these integers)
+    int64_t r[4];
+    if (cell_box) {
+      Tensor res = at::cat({at::stack({bad_box.any().to(at::kLong), first, which, batch.max()}).to(at::kDouble),
+                            boxes.select(0, 0).reshape({9})})
+                       .to(at::kCPU);
+      const double* rd = res.data_ptr<double>();
+      for (int i = 0; i < 4; ++i) r[i] = static_cast<int64_t>(rd[i]);
+      for (int i = 0; i < 9; ++i) box9[i] = rd[4 + i];
+      have_box = true;
+    } else {
+      Tensor res = at::stack({bad_box.any().to(at::kLong), first, which, batch.max()}).to(at::kCPU);
+      for (int i = 0; i < 4; ++i) r[i] = res.data_ptr<int64_t>()[i];
+    }
     static const char* const kMsg[9] = {"box_vectors[0][1] != 0",
                                         "box_vectors[0][2] != 0",
                                         "box_vectors[1][2] != 0",
@@ -174,8 +190,8 @@ Built nl_build(const std::string& strategy_in, const Tensor& pos, const Tensor& 
                                         "box_vectors[0][0] < 2*box_vectors[1][0]",
                                         "box_vectors[1][1] < 2*box_vectors[2][1]"};
     TORCH_CHECK(!r[0], "molecule ", r[1], ": Invalid box vectors: ", kMsg[r[2]]);
-    TORCH_CHECK(r[3] < boxes.size(0), "Expected one box per molecule: \"box_vectors\" has ", boxes.size(0),
-                " boxes, \"batch\" reaches molecule ", r[3]);
+    TORCH_CHECK(cell_box || r[3] < boxes.size(0), "Expected one box per molecule: \"box_vectors\" has ",
+                boxes.size(0), " boxes, \"batch\" reaches molecule ", r[3]);
   } else if ((use_periodic || st == TMDNET_NL_CELL) && box.defined() && box.numel() > 0) {
     TORCH_CHECK(box.dim() == 2 && box.size(0) == 3 && box.size(1) == 3,
                 "Expected \"box_vectors\" to have shape (3, 3)");

@@ -14,7 +14,10 @@ whole forward + autograd force pass: ~600 launches become one graph launch.
 ``GraphedEnergyForces(..., box=boxes)`` captures a periodic evaluation whose cell can change between replays:
 the box -- ``(3, 3)`` or one per molecule ``(n_molecules, 3, 3)`` -- is kept as a static per-molecule device copy
 the captured neighbour build reads, and ``gm(pos_new, box=box_new)`` copies a new one into it before the replay
-(brute / shared strategies; no box is validated during a replay).
+(no box is validated during a replay).  A model whose distance module uses ``strategy="cell"`` keeps ONE device
+box ``(1, 3, 3)`` for all molecules and builds its cell list from it on the device; the cell table has room for the
+construction box with every lattice vector scaled by ``cell_margin``, and a cell that outgrows it is built on a
+coarser grid (exact, slower), not refused.
 
 ``GraphedEnergyForces(..., virial=True)`` also keeps the per-molecule virial of every replay in ``gm.virial``.
 
@@ -38,6 +41,13 @@ def pair_priors(model):
     return [p for p in (getattr(model, "prior_model", None) or []) if isinstance(p, PairPrior)]
 
 
+def cell_bound_of(box, cell_margin):
+    """The host ``(3, 3)`` float64 box that sizes a captured cell list: the first (the only) box of ``box`` with
+    every lattice vector scaled by ``cell_margin``."""
+    b = box.detach().to(device="cpu", dtype=torch.float64).reshape(-1, 3, 3)[0]
+    return b * float(cell_margin)
+
+
 def refuse_pair_priors(model):
     if pair_priors(model):
         raise ValueError("captured training with pair priors (ZBL, D2, Coulomb) is not supported; train "
@@ -46,7 +56,7 @@ def refuse_pair_priors(model):
 
 class GraphedEnergyForces:
     def __init__(self, model, z, pos, batch, edge_capacity=None, margin=1.25, warmup=3, prior_capacity=None,
-                 virial=False, box=None):
+                 virial=False, box=None, cell_margin=1.25):
         if not model.derivative:
             raise ValueError("GraphedEnergyForces captures TorchMD_Net(derivative=True)")
         rep = model.representation_model
@@ -62,12 +72,31 @@ class GraphedEnergyForces:
         # the static box the captured build reads: always one float64 box per molecule on the device (a
         # (3, 3) box is repeated), so a replay follows whatever __call__ copies into it
         self.box = None
+        self.cell_dists = []
         kw = {}
         if box is not None:
-            n_mol = int(self.batch.max()) + 1
             b = box.detach().to(device=dev, dtype=torch.float64)
-            self.box = (b.expand(n_mol, 3, 3) if b.dim() == 2 else b).contiguous().clone()
+            if getattr(rep.distance, "strategy", None) == "cell":
+                # the cell list takes one box: (1, 3, 3) for every molecule (the kernels clamp the molecule
+                # index), built on the device with room for the construction box scaled by cell_margin
+                if b.dim() == 3 and b.shape[0] != 1:
+                    from .kernels import _MOLBOX_CELL_ERROR
+                    raise RuntimeError(_MOLBOX_CELL_ERROR)
+                self.box = b.reshape(1, 3, 3).contiguous().clone()
+                self.cell_dists = [rep.distance]
+                rep.distance.cell_bound = cell_bound_of(self.box, cell_margin)
+            else:
+                n_mol = int(self.batch.max()) + 1
+                self.box = (b.expand(n_mol, 3, 3) if b.dim() == 2 else b).contiguous().clone()
             kw = {"box": self.box}
+        try:
+            self._warm_up_and_capture(model, rep, dev, kw, edge_capacity, margin, warmup, prior_capacity, virial)
+        except BaseException:  # no object, so no release(): the bound must not stay on the model's distance module
+            for d in self.cell_dists:
+                d.cell_bound = None
+            raise
+
+    def _warm_up_and_capture(self, model, rep, dev, kw, edge_capacity, margin, warmup, prior_capacity, virial):
         # eager warm-up: sizes the edge capacity and the molecule count (and validates the boxes)
         y, f = model(self.z, self.pos.clone(), self.batch, **kw)
         dists = _distance_modules(model)
@@ -134,5 +163,7 @@ class GraphedEnergyForces:
     def release(self):
         for d in self.dists:
             d.static_capacity = None
+        for d in self.cell_dists:
+            d.cell_bound = None
         for p in self.priors:
             p.static_capacity = None

@@ -156,11 +156,15 @@ _STRATEGY = {"brute": nat.NL_BRUTE, "shared": nat.NL_SHARED, "cell": nat.NL_CELL
 
 def neighbor_pairs_raw(strategy, pos, batch, box, use_periodic, cutoff_lower, cutoff_upper,
                        max_pairs, loop, include_transpose, pad_output=True, want_csr=False, pairs_out=None,
-                       pair_rows_out=None):
+                       pair_rows_out=None, cell_bound=None):
     """Launch ``tmdnet_nl_build``.  Returns (neighbors, deltas, distances, num_pairs, row_ptr, T).
     ``pairs_out`` = (pair_row [max_pairs], pair_edge [slots]) int32: also number the edge pairs in the
     same launches (the build's pair operands; sorted-row strategies with the transpose map), with the
-    number of pair rows left in ``pair_rows_out`` (int32 [1], optional)."""
+    number of pair rows left in ``pair_rows_out`` (int32 [1], optional).
+    ``cell_bound``: the cell strategy with a device box ``(1, 3, 3)`` -- a host ``(3, 3)`` box that sizes the
+    workspace (the cells the build may use).  Without it the box is read back here and the workspace holds
+    its own grid (a host read: ``build_graph`` refuses that under ``static_capacity`` before calling)."""
+    _check_cell_box(strategy, pos, box, use_periodic, cell_bound, need_bound=False)
     lib = nat.load()
     nat.require_gpu(pos, "get_neighbor_pairs")
     if strategy not in _STRATEGY:
@@ -185,9 +189,8 @@ def neighbor_pairs_raw(strategy, pos, batch, box, use_periodic, cutoff_lower, cu
     periodic_code = int(bool(use_periodic))
     boxes = None
     if use_periodic and box is not None and box.dim() == 3:
-        # per-molecule boxes: a device array, use_periodic = n_boxes + 1 (tmdnet_nl_build); never read here
-        if st == nat.NL_CELL:
-            raise RuntimeError(_MOLBOX_CELL_ERROR)
+        # per-molecule boxes: a device array, use_periodic = n_boxes + 1 (tmdnet_nl_build); never read here.
+        # The cell list takes one such box (n_boxes = 1: the device-box cell build, sized by cell_bound).
         if box.shape[0] == 0 or box.shape[1:] != (3, 3):
             raise RuntimeError('Expected "box_vectors" to have shape (3, 3) or (n_molecules, 3, 3)')
         if box.device != dev:
@@ -196,7 +199,10 @@ def neighbor_pairs_raw(strategy, pos, batch, box, use_periodic, cutoff_lower, cu
         periodic_code = int(boxes.shape[0]) + 1
         box = None
     box9 = _box9(box) if ((use_periodic and boxes is None) or st == nat.NL_CELL) else None
-    if st == nat.NL_CELL:
+    if st == nat.NL_CELL and boxes is not None:
+        # sizes the workspace only, the build takes the device box; without a bound, room for the box itself
+        box9 = _box9(cell_bound if cell_bound is not None else boxes[0])
+    elif st == nat.NL_CELL:
         if box9 is None:
             raise RuntimeError('Expected "box_size" to have shape (3, 3)')
         b = list(box9)
@@ -245,6 +251,25 @@ def validate_box(box, cutoff_upper):
 
 _MOLBOX_CELL_ERROR = ('per-molecule "box_vectors" (n_molecules, 3, 3) are built by the brute and shared '
                       'strategies only: the cell list takes one (3, 3) box')
+_CELL_BOUND_ERROR = ('the cell list with a device box (1, 3, 3) needs "cell_bound", a host (3, 3) box that sizes '
+                     'its workspace, when nothing may be read back (static_capacity)')
+
+
+def _check_cell_box(strategy, pos, box, use_periodic, cell_bound, need_bound):
+    """The refusals of a 3-d box with the cell strategy, before the native library is touched: several boxes;
+    one box that is not on the positions' device; a bound that is not a host-readable (3, 3) box; no bound
+    where one is needed."""
+    if strategy != "cell" or not use_periodic or box is None or box.dim() != 3:
+        return
+    if box.shape[0] > 1:
+        raise RuntimeError(_MOLBOX_CELL_ERROR)
+    if box.shape[0] == 1 and box.shape[1:] == (3, 3) and box.device != pos.device:
+        raise RuntimeError('Expected per-molecule "box_vectors" on the device of "positions"')
+    if cell_bound is not None and tuple(cell_bound.shape) != (3, 3):
+        raise RuntimeError('Expected "cell_bound" to have shape (3, 3)')
+    if cell_bound is None and need_bound:
+        raise RuntimeError(_CELL_BOUND_ERROR)
+
 
 _BOX_CHECK_MESSAGES = ("box_vectors[0][1] != 0", "box_vectors[0][2] != 0", "box_vectors[1][2] != 0",
                        "box_vectors[0][0] < 2*cutoff", "box_vectors[1][1] < 2*cutoff", "box_vectors[2][2] < 2*cutoff",
@@ -252,11 +277,12 @@ _BOX_CHECK_MESSAGES = ("box_vectors[0][1] != 0", "box_vectors[0][2] != 0", "box_
                        "box_vectors[1][1] < 2*box_vectors[2][1]")
 
 
-def validate_boxes(boxes, cutoff_upper, batch=None):
+def validate_boxes(boxes, cutoff_upper, batch=None, read_back=False):
     """``validate_box`` for per-molecule boxes ``(n, 3, 3)``: the same nine checks on every box, evaluated on
     the boxes' device and read back once.  The error is ``validate_box``'s for the first offending molecule,
     prefixed with its index.  With ``batch`` the same read also carries ``batch.max()``: every molecule
-    needs a box (``n > batch.max()``)."""
+    needs a box (``n > batch.max()``).  ``read_back``: the same read also carries the first box, returned as a
+    host float64 ``(3, 3)`` tensor (the device-box cell build sizes its workspace by it)."""
     if boxes.dim() != 3 or boxes.shape[0] == 0 or boxes.shape[1:] != (3, 3):
         raise RuntimeError('Expected "box_vectors" to have shape (3, 3) or (n_molecules, 3, 3)')
     v = boxes.detach().double()
@@ -271,12 +297,19 @@ def validate_boxes(boxes, cutoff_upper, batch=None):
     fields = [bad_box.any().to(torch.int64), first, which]
     if batch is not None and batch.numel():
         fields.append(batch.max().to(device=v.device, dtype=torch.int64))
-    res = torch.stack(fields).tolist()
+    if read_back:  # float64 carries the three small integers (and a molecule index) exactly
+        res = torch.cat([torch.stack(fields).to(torch.float64), v[0].reshape(9)]).tolist()
+        first_box = torch.tensor(res[-9:], dtype=torch.float64).reshape(3, 3)
+        res = [int(r) for r in res[:-9]]
+    else:
+        first_box = None
+        res = torch.stack(fields).tolist()
     if res[0]:
         raise RuntimeError("molecule {}: Invalid box vectors: {}".format(res[1], _BOX_CHECK_MESSAGES[res[2]]))
     if len(res) > 3 and res[3] >= boxes.shape[0]:
         raise RuntimeError('Expected one box per molecule: "box_vectors" has {} boxes, "batch" reaches molecule {}'
                            .format(boxes.shape[0], res[3]))
+    return first_box
 
 
 class _NeighborGeom(Function):
@@ -676,25 +709,31 @@ class DeviceOverflow:
 
 
 def build_graph(pos, batch, cutoff_lower, cutoff_upper, max_num_pairs, loop=True, strategy="brute",
-                box=None, check_errors=True, static_capacity=None, pairs=False):
+                box=None, check_errors=True, static_capacity=None, pairs=False, cell_bound=None):
     """Symmetric (include_transpose) neighbour graph with CSR rows, transpose map and autograd
     deltas/distances.  Mirrors OptimizedDistance(return_vecs=True, resize_to_fit=True) semantics
     (reference models/utils.py:207-269): one host sync reads num_pairs for the overflow check.
     With ``static_capacity`` the graph is sync-free and HIP-graph capturable: every per-edge tensor
     has ``static_capacity`` rows; overflow is reported on the device (``graph.overflow``).
     ``pairs``: the pair numbering of ``pair_index`` is produced by the build itself (sorted-row
-    strategies; the cell list numbers them lazily with tmdnet_pair_index)."""
+    strategies; the cell list numbers them lazily with tmdnet_pair_index).
+    ``cell_bound``: the cell strategy with one device box ``(1, 3, 3)`` -- a host ``(3, 3)`` box that bounds the
+    cells the build gets room for (a larger cell is built on a coarser grid).  Eager calls without it size the
+    workspace for the box itself, read back with the box checks; with ``static_capacity`` it is required."""
     use_periodic = box is not None and box.numel() > 0
     if use_periodic and box.dim() == 3:
-        # per-molecule boxes (n_boxes, 3, 3) on the device: brute / shared.  Eager: the nine checks per box
-        # and n_boxes > batch.max() in one host read, before anything is launched.  Static capacity: no host
-        # read at all -- the warm-up call checked the sizes and the kernel clamps the molecule index.
-        if strategy == "cell":
-            raise RuntimeError(_MOLBOX_CELL_ERROR)
+        # per-molecule boxes (n_boxes, 3, 3) on the device: brute / shared; the cell list takes one (1, 3, 3),
+        # which serves every molecule.  Eager: the nine checks per box and n_boxes > batch.max() in one host
+        # read, before anything is launched.  Static capacity: no host read at all -- the warm-up call checked
+        # the sizes and the kernel clamps the molecule index.
+        _check_cell_box(strategy, pos, box, use_periodic, cell_bound, need_bound=static_capacity is not None)
         if box.device != pos.device:
             raise RuntimeError('Expected per-molecule "box_vectors" on the device of "positions"')
+        one_cell_box = strategy == "cell" and box.shape[0] == 1
         if static_capacity is None:
-            validate_boxes(box, cutoff_upper, batch)
+            read = validate_boxes(box, cutoff_upper, None if one_cell_box else batch, read_back=one_cell_box)
+            if one_cell_box and cell_bound is None:
+                cell_bound = read  # the box itself, from the same host read as its checks
     elif use_periodic:
         validate_box(box, cutoff_upper)
     if strategy == "cell" and not use_periodic:
@@ -713,7 +752,8 @@ def build_graph(pos, batch, cutoff_lower, cutoff_upper, max_num_pairs, loop=True
         nrows = torch.empty((1,), dtype=torch.int32, device=pos.device) if fused_pairs is not None else None
         nb, dl, dist, num, row_ptr, tr = neighbor_pairs_raw(
             strategy, pos, batch, box, use_periodic, cutoff_lower, cutoff_upper, cap, loop,
-            True, pad_output=True, want_csr=True, pairs_out=fused_pairs, pair_rows_out=nrows)
+            True, pad_output=True, want_csr=True, pairs_out=fused_pairs, pair_rows_out=nrows,
+            cell_bound=cell_bound)
         graph = EdgeGraph(pos.shape[0], row_ptr, nb[0], nb[1], tr, None, None, None, symmetric=True,
                           static=True)
         graph.num_pairs_dev = num
@@ -730,7 +770,7 @@ def build_graph(pos, batch, cutoff_lower, cutoff_upper, max_num_pairs, loop=True
         return graph
     nb, dl, dist, num, row_ptr, tr = neighbor_pairs_raw(
         strategy, pos, batch, box, use_periodic, cutoff_lower, cutoff_upper, max_num_pairs, loop,
-        True, pad_output=False, want_csr=True, pairs_out=fused_pairs)
+        True, pad_output=False, want_csr=True, pairs_out=fused_pairs, cell_bound=cell_bound)
     num_pairs = int(num.item())
     cap = int(max_num_pairs)
     if check_errors and num_pairs > cap:

@@ -214,6 +214,9 @@ class OptimizedDistance(torch.nn.Module):
         self.static_capacity = None
         # graph(): number the edge pairs in the build itself (the ET consumer sets it; sorted rows)
         self.pair_rows = False
+        # strategy "cell" with a per-call device box (1, 3, 3): a host (3, 3) box that bounds the cells the
+        # build gets room for (kernels.build_graph; required with static_capacity, where nothing is read back)
+        self.cell_bound = None
 
     def _max_pairs(self, n: int) -> int:
         return -self.max_num_pairs * n if self.max_num_pairs < 0 else self.max_num_pairs
@@ -221,7 +224,10 @@ class OptimizedDistance(torch.nn.Module):
     def forward(self, pos: Tensor, batch: Optional[Tensor] = None,
                 box: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
         """``box``: a box for this call, ``(3, 3)`` or per molecule ``(n_molecules, 3, 3)`` (on the positions'
-        device; brute / shared); it wins over the constructor's.  ``None``: the constructor's box."""
+        device; brute / shared, or one box ``(1, 3, 3)`` for the cell list); it wins over the constructor's.
+        ``None``: the constructor's box.  The op behind this call keeps the reference's schema, which has no
+        place for ``cell_bound``: it reads a ``(1, 3, 3)`` cell box back with its checks and gives the build
+        room for exactly that box (``graph`` is the route that takes the bound)."""
         self.box = self.box.to(pos.dtype)
         max_pairs = self._max_pairs(pos.shape[0])
         if batch is None:
@@ -270,7 +276,8 @@ class OptimizedDistance(torch.nn.Module):
         g = kernels.build_graph(pos, batch, self.cutoff_lower, self.cutoff_upper,
                                 self._max_pairs(pos.shape[0]), loop=self.loop, strategy=strategy,
                                 box=box, check_errors=self.check_errors,
-                                static_capacity=self.static_capacity, pairs=self.pair_rows)
+                                static_capacity=self.static_capacity, pairs=self.pair_rows,
+                                cell_bound=self.cell_bound)
         # keep only the device-side status of the last build (static-capacity overflow flag, pair
         # count): holding the graph itself would keep its autograd history -- and the positions'
         # AccumulateGrad node -- alive across steps, which breaks HIP-graph capture of later steps
