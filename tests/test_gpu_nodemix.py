@@ -16,6 +16,22 @@ def _rel(a, b):
     return float((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(1e-30))
 
 
+ULP = 2.0 ** -24
+
+
+def _bar(miss, name, got, ref64, comp32):
+    """The fp32 bar of test_gpu_et_widths.py / test_gpu_gemm_edges.py against an fp64 reference:
+    e_k <= 2 e_c + 4 * 2**-24 * scale, e_c the error of the same expression evaluated by torch in fp32 on the GPU.
+    Prints the figures; appends a miss."""
+    ref64 = ref64.reshape(got.shape)
+    scale = float(ref64.abs().max())
+    e_k = float((got.double() - ref64).abs().max())
+    e_c = float((comp32.reshape(got.shape).double() - ref64).abs().max())
+    print(f"NODEMIX|{name}|e_k {e_k:.3g}|e_c {e_c:.3g}|scale {scale:.3g}|ratio {e_k / max(e_c, 1e-300):.3g}")
+    if not e_k <= 2 * e_c + 4 * ULP * scale:
+        miss.append((name, e_k, e_c, scale))
+
+
 def _inputs(N, H, first, seed=0):
     g = torch.Generator().manual_seed(seed)
     r = lambda *s: torch.randn(*s, generator=g).to(DEV)  # noqa: E731
@@ -27,7 +43,8 @@ def _inputs(N, H, first, seed=0):
 
 
 @pytest.mark.parametrize("N,H,first", [(678, 128, False), (678, 128, True), (37, 64, False), (100, 256, False),
-                                       (1, 128, False)])
+                                       (1, 128, False), (31, 192, False), (32, 192, True), (33, 192, False),
+                                       (100, 192, False), (31, 128, True), (32, 64, False), (33, 256, False)])
 def test_oproj_epilogue_matches_two_launch_form(N, H, first):
     from torchmdnet import et_stack, kernels
     xa, x, vec, vecp, veca, o_w, o_b = _inputs(N, H, first)
@@ -51,10 +68,24 @@ def test_oproj_epilogue_matches_two_launch_form(N, H, first):
         xt = x.double() + (v1 * v2).sum(1) * o2 + o3
         vt = vec.double() + v3 * o1.unsqueeze(1) + veca.double()
     assert _rel(o, ot) < 1e-5 and _rel(xo, xt) < 1e-5 and _rel(vo, vt) < 1e-5
+    # and at the fp32 bar, against the same expressions evaluated by torch in fp32
+    oc = torch.addmm(o_b, xa, o_w.t())
+    c1, c2, c3 = oc.split(H, dim=1)
+    if first:
+        xc, vc = x + c3, veca
+    else:
+        w1, w2, w3 = vecp.split(H, dim=2)
+        xc = x + (w1 * w2).sum(1) * c2 + c3
+        vc = vec + w3 * c1.unsqueeze(1) + veca
+    miss = []
+    for name, got, ref, comp in (("o", o, ot, oc), ("x_out", xo, xt, xc), ("vec_out", vo, vt, vc)):
+        _bar(miss, f"oproj_epi N={N} H={H} first={first} {name}", got, ref, comp)
+    assert not miss, miss
 
 
 @pytest.mark.parametrize("N,H,with_vec", [(678, 128, True), (678, 128, False), (37, 64, True), (100, 256, True),
-                                          (1, 128, True)])
+                                          (1, 128, True), (31, 192, True), (32, 192, False), (33, 192, True),
+                                          (100, 192, True), (31, 128, True), (32, 64, True), (33, 256, True)])
 def test_ln_mix_matches_layer_norm_and_linears(N, H, with_vec):
     from torchmdnet import et_stack
     g = torch.Generator().manual_seed(1)
@@ -83,9 +114,23 @@ def test_ln_mix_matches_layer_norm_and_linears(N, H, with_vec):
         assert _rel(vecp.reshape(3 * N, 3 * H), vr) < 1e-5
     else:
         assert vecp is None
+    # and at the fp32 bar, against the same expressions evaluated by torch in fp32
+    xn_c = torch.nn.functional.layer_norm(x, (H,), ln_w, ln_b, 1e-5)
+    mean_c = x.mean(1, keepdim=True)
+    rstd_c = 1 / torch.sqrt(x.var(1, unbiased=False, keepdim=True) + 1e-5)
+    miss = []
+    what = f"ln_mix N={N} H={H} vec={with_vec}"
+    _bar(miss, f"{what} xn", xn, xn_ref, xn_c)
+    _bar(miss, f"{what} mean", mean, m, mean_c)
+    _bar(miss, f"{what} rstd", rstd, rs, rstd_c)
+    _bar(miss, f"{what} qkv", qkv, xn_ref @ w.double().t() + b.double(), torch.addmm(b, xn_c, w.t()))
+    if with_vec:
+        _bar(miss, f"{what} vecp", vecp, vr, vec.reshape(3 * N, H) @ vec_w.t())
+    assert not miss, miss
 
 
-@pytest.mark.parametrize("N,first,res", [(678, False, True), (678, True, True), (37, False, False), (1, False, True)])
+@pytest.mark.parametrize("N,first,res", [(678, False, True), (678, True, True), (37, False, False), (1, False, True),
+                                         (31, False, True), (32, True, False), (33, False, True)])
 def test_lnbwd_oproj_matches_two_launch_form(N, first, res):
     """tmdnet_et_lnbwd_oproj_f32 against tmdnet_ln_bwd_epilogue + the o_proj input-gradient GEMM."""
     from torchmdnet import et_stack, kernels
