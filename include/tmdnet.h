@@ -84,10 +84,14 @@ enum { TMDNET_ACT_SILU = 0, TMDNET_ACT_SSP = 1, TMDNET_ACT_TANH = 2, TMDNET_ACT_
  * tmdnet_nl_workspace_bytes sizes the cell arrays by the same rule from box9.
  * use_periodic: 0 = no box; 1 = the one host box in box9 (above); k >= 2 = per-molecule boxes: box9 is then
  * a DEVICE pointer to k - 1 boxes, [k - 1][9] doubles, row-major a, b, c each, in the same reduced triclinic
- * form, and every atom of molecule m = batch[t] is imaged in box m (all molecules periodic).  Each wave
- * reads its destination's box once and converts it as the host box is converted, so a stack of equal
- * boxes gives bitwise the single-box list.  The molecule index is clamped to [0, k - 2] before the array
- * is indexed: a batch value outside it gives wrong pairs, never a read outside the array.  The host does
+ * form, and every atom of molecule m = batch[t] is imaged in box m.  A box whose nine entries are all == 0
+ * means molecule m has no box (an open molecule): its pairs are the non-periodic ones, deltas = pos[src] -
+ * pos[dst] with no image, bitwise those of use_periodic = 0.  Each wave reads its destination's box once
+ * (all nine entries; the decision is uniform over the wave) and converts it as the host box is converted, so
+ * a stack of equal boxes gives bitwise the single-box list.  A box that is neither all-zero nor of the reduced
+ * form gives a meaningless list, never an access outside a buffer.  The molecule index is clamped to
+ * [0, k - 2] before the array is indexed: a batch value outside it gives wrong pairs, never a read outside
+ * the array.  The host does
  * not read or validate the boxes.  Several boxes are brute and shared only: the cell strategy with k >= 3
  * is TMDNET_UNSUPPORTED; a NULL box9 with k >= 2 is TMDNET_BAD_ARGUMENT (nothing launched in either case).
  * tmdnet_nl_workspace_bytes takes a host box9 (or NULL) as before: brute and shared size nothing by it.
@@ -105,7 +109,8 @@ enum { TMDNET_ACT_SILU = 0, TMDNET_ACT_SSP = 1, TMDNET_ACT_TANH = 2, TMDNET_ACT_
  * below 3.  The list stays exact: a skewed box is binned in thicker fractional cells; a diagonal box keeps
  * cutoff-wide cells and folds every atom past the last one into cell 0, which the first and the last cell
  * both scan -- with room for few cells that build approaches all pairs.  A
- * degenerate or non-finite device box gives a meaningless list, never an access outside a buffer.  The fill of
+ * degenerate or non-finite device box gives a meaningless list, never an access outside a buffer; the device-box
+ * cell build needs a real box, and an all-zero one is that degenerate case here, not an open molecule.  The fill of
  * the cell table and the sort's key width follow the capacity, not the grid.
  * Pair numbering (optional): pair_row [max_pairs] and pair_edge [n_pair_slots > 0] given together are filled
  * as tmdnet_pair_index fills them, with no extra launch (the canonical counts ride on the count pass, their

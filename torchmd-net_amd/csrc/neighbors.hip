@@ -81,13 +81,18 @@ template <typename T> struct Params {
 // The box of molecule `m` (wave-uniform: one wave serves one destination, and its candidates are its own
 // molecule's) from the device array, converted as the host path converts its one box ((T)box[i]).  The
 // index is clamped, so a batch value outside the boxes reads a box of the array, never past it, and is
-// made provably uniform (readfirstlane), so the six entries come through the scalar cache once per wave.
+// made provably uniform (readfirstlane), so the nine entries come through the scalar cache once per wave.
+// `open`: all nine entries are zero -- the molecule has no box (its pairs take no image).  The three
+// entries above the diagonal count for that alone; the comparison is made on the doubles, before the
+// conversion, so a box whose entries merely underflow in T is not open.
 template <typename T>
-__device__ __forceinline__ Tric<T> load_mol_box(const Params<T>& P, int64_t m) {
+__device__ __forceinline__ Tric<T> load_mol_box(const Params<T>& P, int64_t m, bool& open) {
   const int64_t last = (int64_t)P.n_boxes - 1;
   const int mi = __builtin_amdgcn_readfirstlane((int)(m < 0 ? 0 : (m > last ? last : m)));
   const double* b = P.boxes + (size_t)9 * mi;
-  return {(T)b[0], (T)b[3], (T)b[4], (T)b[6], (T)b[7], (T)b[8]};
+  const double a0 = b[0], b0 = b[3], b1 = b[4], c0 = b[6], c1 = b[7], c2 = b[8];
+  open = a0 == 0 && b[1] == 0 && b[2] == 0 && b0 == 0 && b1 == 0 && b[5] == 0 && c0 == 0 && c1 == 0 && c2 == 0;
+  return {(T)a0, (T)b0, (T)b1, (T)c0, (T)c1, (T)c2};
 }
 
 // Directed edge s -> t (neighbors[0]=s, neighbors[1]=t): delta = pos[s] - pos[t] (minimum image).
@@ -150,8 +155,11 @@ __global__ __launch_bounds__(256) void k_segments(const int64_t* __restrict__ ba
 // Count pass with `ccounts`: also the number of canonical sources (s >= t) per row -- the pair
 // numbering of the sorted rows (see k_transpose) needs nothing else.
 // MOLBOX: every molecule has its own periodic box (P.boxes); the destination's is fetched once, before
-// the candidate loop, and takes the place of P.box in the same Tric::apply.  The single-box
-// instantiations (MOLBOX false) are the statements they were.
+// the candidate loop, and takes the place of P.box in the same Tric::apply.  An all-zero box is an open
+// molecule: the wave clears its own copy of P.periodic (kernel arguments are wave-uniform, so this is one
+// scalar select, no second instantiation), and edge_delta then skips the image as it does without a box --
+// nothing divides by the zero entries.  The single-box instantiations (MOLBOX false) are the statements
+// they were.
 template <typename T, bool FILL, bool MOLBOX = false>
 __global__ __launch_bounds__(256) void k_pairs(Params<T> P, const int* __restrict__ seg,
                                                int* __restrict__ counts, const int* __restrict__ row_ptr,
@@ -166,7 +174,11 @@ __global__ __launch_bounds__(256) void k_pairs(Params<T> P, const int* __restric
   const int lo = all ? 0 : seg[2 * t], hi = all ? P.n : seg[2 * t + 1];
   const V3<T> pt = load3(P.pos, t);
   const int64_t bt = P.batch[t];
-  if (MOLBOX) P.box = load_mol_box(P, bt);
+  if (MOLBOX) {
+    bool open;
+    P.box = load_mol_box(P, bt, open);
+    if (open) P.periodic = 0;
+  }
   int off = FILL ? row_ptr[t] : 0;
   int coff = 0;
   for (int base = lo; base < hi; base += TMD_WAVE) {

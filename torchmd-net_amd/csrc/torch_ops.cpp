@@ -144,6 +144,7 @@ Built nl_build(const std::string& strategy_in, const Tensor& pos, const Tensor& 
   bool have_box = false;
   // per-molecule boxes (n_boxes, 3, 3): a float64 device array, use_periodic = n_boxes + 1 (tmdnet_nl_build);
   // the nine checks per box and n_boxes > batch.max() on the device, one host read, before any launch.
+  // An all-zero box among several is an open molecule and passes.
   // The cell list takes one such box, (1, 3, 3), for every molecule (the device-box cell build): the same
   // read brings the box back, and the workspace is sized for exactly that box.
   Tensor boxes;
@@ -163,6 +164,8 @@ Built nl_build(const std::string& strategy_in, const Tensor& pos, const Tensor& 
                            e(0, 0) >= 2 * e(1, 0), e(0, 0) >= 2 * e(2, 0), e(1, 1) >= 2 * e(2, 1)},
                           1);
     Tensor bad = ok.logical_not();
+    // among several boxes an all-zero one passes: that molecule is open (tmdnet_nl_build); a lone one does not
+    if (boxes.size(0) > 1) bad = bad.logical_and((boxes != 0).reshape({-1, 9}).any(1, true));
     Tensor bad_box = bad.any(1);
     Tensor first = bad_box.to(at::kLong).argmax();
     Tensor which = bad.index_select(0, first.reshape({1})).reshape({9}).to(at::kLong).argmax();

@@ -23,7 +23,11 @@ coarser grid (exact, slower), not refused.
 
 Pair priors (ZBL, D2, Coulomb) build a neighbour list of their own: each gets its own static capacity from its
 own warm-up pair count (``prior_capacity`` overrides it for all of them) and its own overflow flag, which
-``check_capacity`` reads besides the representation model's.
+``check_capacity`` reads besides the representation model's.  A prior built with ``periodic=True`` reads the same
+static box as the model, so its list follows ``gm(pos, box=new)`` too; one with ``neighbor_strategy="cell"`` needs
+that box to be a single one, and gets the same ``cell_margin`` bound for its cell table.  A model on brute / shared
+keeps one static box per molecule, also when one ``(3, 3)`` box was given, so beside such a model a ``"cell"`` prior is
+captured over a single molecule only (the eager call has no such limit); put the model on the cell list too.
 """
 import math
 
@@ -72,7 +76,7 @@ class GraphedEnergyForces:
         # the static box the captured build reads: always one float64 box per molecule on the device (a
         # (3, 3) box is repeated), so a replay follows whatever __call__ copies into it
         self.box = None
-        self.cell_dists = []
+        self.cell_dists = []  # the modules whose cell_bound this object set: distance modules and "cell" priors
         kw = {}
         if box is not None:
             b = box.detach().to(device=dev, dtype=torch.float64)
@@ -88,6 +92,24 @@ class GraphedEnergyForces:
             else:
                 n_mol = int(self.batch.max()) + 1
                 self.box = (b.expand(n_mol, 3, 3) if b.dim() == 2 else b).contiguous().clone()
+            # a periodic prior on the cell list builds from the same static box, which must then be one box
+            cell_priors = [p for p in pair_priors(model) if p.periodic and p.neighbor_strategy == "cell"]
+            if cell_priors and self.box.shape[0] != 1:
+                from .kernels import _MOLBOX_CELL_ERROR
+                for d in self.cell_dists:
+                    d.cell_bound = None
+                if b.dim() == 2:
+                    # one box was given, but a model on brute / shared reads it as one static box per molecule,
+                    # and the prior reads what the model reads
+                    raise RuntimeError('a pair prior with neighbor_strategy="cell" is captured with one box beside a '
+                                       'model whose distance module is on the cell list too, or over a single '
+                                       f'molecule: this batch has {self.box.shape[0]} molecules and the model\'s '
+                                       f'strategy is "{getattr(rep.distance, "strategy", None)}", which keeps one '
+                                       'static box per molecule')
+                raise RuntimeError(_MOLBOX_CELL_ERROR)
+            for p in cell_priors:  # the bound is set here and cleared where the distance module's is
+                p.cell_bound = cell_bound_of(self.box, cell_margin)
+            self.cell_dists = self.cell_dists + cell_priors
             kw = {"box": self.box}
         try:
             self._warm_up_and_capture(model, rep, dev, kw, edge_capacity, margin, warmup, prior_capacity, virial)

@@ -282,7 +282,10 @@ def validate_boxes(boxes, cutoff_upper, batch=None, read_back=False):
     the boxes' device and read back once.  The error is ``validate_box``'s for the first offending molecule,
     prefixed with its index.  With ``batch`` the same read also carries ``batch.max()``: every molecule
     needs a box (``n > batch.max()``).  ``read_back``: the same read also carries the first box, returned as a
-    host float64 ``(3, 3)`` tensor (the device-box cell build sizes its workspace by it)."""
+    host float64 ``(3, 3)`` tensor (the device-box cell build sizes its workspace by it).
+    Among several boxes an all-zero one (all nine entries ``== 0``) passes: that molecule is open, its pairs take
+    no image.  A partly-zero box fails its checks as any other, and so does a lone all-zero box (``n == 1``:
+    pass ``box=None``)."""
     if boxes.dim() != 3 or boxes.shape[0] == 0 or boxes.shape[1:] != (3, 3):
         raise RuntimeError('Expected "box_vectors" to have shape (3, 3) or (n_molecules, 3, 3)')
     v = boxes.detach().double()
@@ -291,6 +294,8 @@ def validate_boxes(boxes, cutoff_upper, batch=None, read_back=False):
                       v[:, 2, 2] >= c2, v[:, 0, 0] >= 2 * v[:, 1, 0], v[:, 0, 0] >= 2 * v[:, 2, 0],
                       v[:, 1, 1] >= 2 * v[:, 2, 1]], dim=1)
     bad = ~ok
+    if boxes.shape[0] > 1:  # an open molecule among the boxes
+        bad = bad & (v != 0).reshape(-1, 9).any(dim=1, keepdim=True)
     bad_box = bad.any(dim=1)
     first = bad_box.to(torch.int64).argmax()  # argmax of a 0/1 vector: its first 1
     which = bad[first].to(torch.int64).argmax()

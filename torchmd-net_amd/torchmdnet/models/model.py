@@ -252,6 +252,24 @@ class TorchMD_Net(nn.Module):
         return state
 
     @torch.jit.unused
+    def _post_reduce_priors(self, y: Tensor, z: Tensor, pos: Tensor, batch: Tensor,
+                            extra_args: Optional[Dict[str, Tensor]], box: Optional[Tensor]) -> Tensor:
+        """Every prior's ``post_reduce``.  The pair priors also get the call's box, through ``post_reduce_box``,
+        which only they have (a user's own five-argument ``BasePrior`` keeps working): ``box`` if given, else the
+        distance module's own when that module is periodic.  A prior built without ``periodic=True`` ignores it."""
+        from ..priors.pair import PairPrior
+        if box is None:
+            dist = getattr(self.representation_model, "distance", None)
+            if dist is not None and getattr(dist, "use_periodic", False):
+                box = dist.box.to(pos.dtype)
+        for prior in self.prior_model:
+            if isinstance(prior, PairPrior):
+                y = prior.post_reduce_box(y, z, pos, batch, extra_args, box)
+            else:
+                y = prior.post_reduce(y, z, pos, batch, extra_args)
+        return y
+
+    @torch.jit.unused
     def _early_dim_size(self, batch: Tensor) -> None:
         """The molecule count read back now, while the queue is short: at the reduction the read-back would
         wait out the whole enqueued forward before the force pass could be enqueued (eager evaluation)."""
@@ -262,9 +280,12 @@ class TorchMD_Net(nn.Module):
                 s: Optional[Tensor] = None, extra_args: Optional[Dict[str, Tensor]] = None,
                 box: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
         """``box``: the periodic box of this call, ``(3, 3)`` or one per molecule ``(n_molecules, 3, 3)`` on the
-        positions' device (brute / shared neighbour strategies, every molecule periodic); it wins over the box
+        positions' device (brute / shared neighbour strategies); it wins over the box
         the representation model's distance module was built with.  Eager only: the neighbour list is then
-        built by the Python graph path, and the scripted model raises.  The pair priors stay non-periodic."""
+        built by the Python graph path, and the scripted model raises.  Among several boxes an all-zero one means
+        that molecule has no box (an open molecule beside periodic ones).  A pair prior built with
+        ``periodic=True`` (ZBL, D2) builds its own list under the same box -- this argument, else the distance
+        module's own -- with its own cutoff; the others stay non-periodic."""
         assert z.dim() == 1 and z.dtype == torch.long
         batch = torch.zeros_like(z) if batch is None else batch
         if torch.jit.is_scripting():
@@ -306,8 +327,7 @@ class TorchMD_Net(nn.Module):
                 x = x + self.mean
         y = self.output_model.post_reduce(x)
         if self.prior_model is not None:
-            for prior in self.prior_model:
-                y = prior.post_reduce(y, z, pos, batch, extra_args)
+            y = self._post_reduce_priors(y, z, pos, batch, extra_args, box)
         if self.derivative:
             # -dy/dpos directly: the backward is seeded with -1 instead of negating its result (sign
             # flips are exact; one elementwise launch fewer than the reference's `-dy`, model.py:298)

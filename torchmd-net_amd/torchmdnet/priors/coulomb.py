@@ -17,10 +17,14 @@ from typing import Dict, Optional
 import torch
 from torch import Tensor
 
-from .pair import PairPrior
+from .pair import PairPrior, box_options
 
 
 class Coulomb(PairPrior):
+    periodic_refusal = ("this prior has an infinite cutoff, which has no meaning under periodic images (a periodic "
+                        "Coulomb sum needs an Ewald method)")
+
+    @box_options
     def __init__(self, alpha, max_num_neighbors, distance_scale=None, energy_scale=None, dataset=None):
         super().__init__()
         if distance_scale is None:

@@ -10,14 +10,15 @@ in J/mol with R in nm, then converted with ``energy_scale`` (energies -> joules,
 ``Z_map``, ``C_6`` and ``R_r`` are the state_dict buffers.  Elements beyond Xe have no parameters (NaN, as in
 the reference: their energy is NaN rather than silently zero).
 
-No box, total-pairs overflow, own ``static_capacity``: see ``priors/pair.py``.  ``post_reduce`` does not
+Non-periodic unless ``periodic=True`` (then the list is built under the call's box, by ``neighbor_strategy``),
+total-pairs overflow, own ``static_capacity``: see ``priors/pair.py``.  ``post_reduce`` does not
 script (``torch.jit.unused``): a scripted model holding this prior compiles and raises when called."""
 from typing import Dict, Optional
 
 import torch
 from torch import Tensor
 
-from .pair import PairPrior
+from .pair import PairPrior, box_options
 
 _NAN = float("nan")
 # Table 1 of Grimme 2006, H .. Xe: C6 in J mol^-1 nm^6 and the van der Waals radius R_0 in Angstrom
@@ -45,6 +46,7 @@ def _table() -> Tensor:
 class D2(PairPrior):
     C_6_R_r = _table()
 
+    @box_options
     def __init__(self, cutoff_distance, max_num_neighbors, atomic_number=None, distance_scale=None,
                  energy_scale=None, dataset=None, dtype=torch.float32):
         super().__init__()
@@ -66,7 +68,8 @@ class D2(PairPrior):
                 "max_num_neighbors": self.max_num_neighbors,
                 "atomic_number": self.atomic_number,
                 "distance_scale": self.distance_scale,
-                "energy_scale": self.energy_scale}
+                "energy_scale": self.energy_scale,
+                **self._periodic_args()}
 
     def constants(self):
         """(k_e, r -> nm, d) in double: phi = -k_e a_i a_j / R^6 / (1 + exp(-d (R / (b_i + b_j) - 1)))."""
@@ -75,7 +78,13 @@ class D2(PairPrior):
     @torch.jit.unused
     def post_reduce(self, y: Tensor, z: Tensor, pos: Tensor, batch: Tensor,
                     extra_args: Optional[Dict[str, Tensor]]):
-        graph = self._graph(pos, batch, float(self.cutoff_distance))
+        return self.post_reduce_box(y, z, pos, batch, extra_args, None)
+
+    @torch.jit.unused
+    def post_reduce_box(self, y: Tensor, z: Tensor, pos: Tensor, batch: Tensor,
+                        extra_args: Optional[Dict[str, Tensor]], box: Optional[Tensor]):
+        """``post_reduce`` under the call's box (``None``, or a prior built without ``periodic=True``: no box)."""
+        graph = self._graph(pos, batch, float(self.cutoff_distance), box, y.shape[0])
         Z = self.Z_map.index_select(0, z)
         a = self.C_6.index_select(0, Z).to(pos.dtype).sqrt()
         b = self.R_r.index_select(0, Z).to(pos.dtype)

@@ -8,7 +8,8 @@ the arguments) give ``atomic_number`` (atom type -> atomic number), ``distance_s
 and ``energy_scale`` (energies -> joules, not J/mol).  ``atomic_number`` is the one state_dict buffer.
 
 Z^0.23 is formed in the dtype of the positions (the reference rounds it to float32 even in a float64 model).
-No box, total-pairs overflow, own ``static_capacity``: see ``priors/pair.py``.  ``post_reduce`` does not
+Non-periodic unless ``periodic=True`` (then the list is built under the call's box, by ``neighbor_strategy``),
+total-pairs overflow, own ``static_capacity``: see ``priors/pair.py``.  ``post_reduce`` does not
 script (``torch.jit.unused``): a scripted model holding this prior compiles and raises when called."""
 import math
 from typing import Dict, Optional
@@ -16,12 +17,13 @@ from typing import Dict, Optional
 import torch
 from torch import Tensor
 
-from .pair import PairPrior
+from .pair import PairPrior, box_options
 
 _BOHR = 5.29177210903e-11  # metres
 
 
 class ZBL(PairPrior):
+    @box_options
     def __init__(self, cutoff_distance, max_num_neighbors, atomic_number=None, distance_scale=None,
                  energy_scale=None, dataset=None):
         super().__init__()
@@ -42,7 +44,8 @@ class ZBL(PairPrior):
                 "max_num_neighbors": self.max_num_neighbors,
                 "atomic_number": self.atomic_number.tolist(),
                 "distance_scale": self.distance_scale,
-                "energy_scale": self.energy_scale}
+                "energy_scale": self.energy_scale,
+                **self._periodic_args()}
 
     def constants(self):
         """(k_e, k_a, cutoff, pi / cutoff) in double: phi = k_e Z_i Z_j / r * f(r k_a (b_i + b_j)) * C(r)."""
@@ -53,6 +56,12 @@ class ZBL(PairPrior):
     @torch.jit.unused
     def post_reduce(self, y: Tensor, z: Tensor, pos: Tensor, batch: Tensor,
                     extra_args: Optional[Dict[str, Tensor]]):
-        graph = self._graph(pos, batch, float(self.cutoff_distance))
+        return self.post_reduce_box(y, z, pos, batch, extra_args, None)
+
+    @torch.jit.unused
+    def post_reduce_box(self, y: Tensor, z: Tensor, pos: Tensor, batch: Tensor,
+                        extra_args: Optional[Dict[str, Tensor]], box: Optional[Tensor]):
+        """``post_reduce`` under the call's box (``None``, or a prior built without ``periodic=True``: no box)."""
+        graph = self._graph(pos, batch, float(self.cutoff_distance), box, y.shape[0])
         Z = self.atomic_number.index_select(0, z).to(pos.dtype)
         return self._add_energy(y, "zbl", graph, Z, Z.pow(0.23), self.constants(), batch)

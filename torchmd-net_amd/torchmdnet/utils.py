@@ -32,7 +32,8 @@ class MissingEnergyException(Exception):
 def stress_from_virial(virial, box):
     """Stress of every molecule from ``TorchMD_Net.energy_forces_virial``'s virial ``[n_mol, 3, 3]``
     (``-dE_m/d eps``): ``-virial[m] / det(box_m)``, the inverse of the label convention
-    ``virial = -stress * det(box)``.  ``box``: ``(3, 3)`` (one cell for all) or ``(n_mol, 3, 3)``."""
+    ``virial = -stress * det(box)``.  ``box``: ``(3, 3)`` (one cell for all) or ``(n_mol, 3, 3)``.  Stress is
+    undefined for an open molecule (an all-zero box): its volume is zero, the division is the caller's business."""
     b = box.to(device=virial.device, dtype=virial.dtype).reshape(-1, 3, 3)
     vol = (b[:, 0, 0] * (b[:, 1, 1] * b[:, 2, 2] - b[:, 1, 2] * b[:, 2, 1])
            - b[:, 0, 1] * (b[:, 1, 0] * b[:, 2, 2] - b[:, 1, 2] * b[:, 2, 0])
