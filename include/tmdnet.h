@@ -48,10 +48,38 @@ enum { TMDNET_ET_TWO_PASS = 64 };
  * The backward takes it in dr mode only, without gpk / gpv (the raw-row gradient cannot be formed from
  * S): gdist == NULL or gpk / gpv != NULL -> TMDNET_BAD_ARGUMENT, nothing written.  It runs the one-grid or
  * the two-launch form, never the merged pass.
- * Values in use -- forward flags: 4 (V_PLANAR), 128 (PREACT), 0xff00 (ACT); backward accumulate: 1, 2
- * (ACC_VEC_RESIDUAL, ACC_EDGE), 4, 32 (ACC_GRADS), 64 (TWO_PASS), 128, 0xff00; _bwd2 flags: 4, 8, 16
- * (BWD2_ACC_*), 0xff00. */
+ * Values in use -- forward flags: 4 (V_PLANAR), 128 (PREACT), 0xff00 (ACT), 0x10000 (SCALAR); backward
+ * accumulate: 1, 2 (ACC_VEC_RESIDUAL, ACC_EDGE), 4, 32 (ACC_GRADS), 64 (TWO_PASS), 128, 0xff00, 0x10000;
+ * _bwd2 flags: 4, 8, 16 (BWD2_ACC_*), 0xff00, 0x10000. */
 enum { TMDNET_ET_PREACT = 128 };
+/* tmdnet_et_message_fwd flags / _bwd accumulate / _bwd2 flags: the SCALAR form of the message, the invariant
+ * Transformer's (reference MultiHeadAttention.message, models/torchmd_t.py:246-283) -- the ET message with
+ * the vector channels removed.  For edge e = (t <- s), head h, channel c of the head:
+ *     sc[e,h]    = sum_c q[t,h,c] k[s,h,c] A(pk[e,h,c])             (pk NULL: factor 1)
+ *     a[e,h]     = B(sc[e,h]) * C[e]
+ *     out[t,h,c] = sum_{e in row t} v[s,h,c] A(pv[e,h,c]) a[e,h]    (pv NULL: factor 1)
+ * A / B: the dk / dv and the attention activation of the TMDNET_ET_ACT bits, all four at run time.  q, k, v:
+ * [N][H] (ld_q / ld_k / ld_v); pk, pv: [E][H] pre-activation rows (ld_pk / ld_pv; each nullable; they may be
+ * column blocks of one [E][2H] buffer); cutoff [E]; x_out [N][H].  4H values move per edge (2H streamed, 2H
+ * gathered) where the vector form with v / pv padded to 3H moves 8H.  `order` is honoured (same bits).
+ * The operands of the vector form must be absent -- NULL: vec_in, unit, vec_out, grad_vec, gvec_in, gunit,
+ * dpk, dpv, gdist, gg_vec, gg_unit, d_grad_vec, d_vec, d_unit, pk_rows, gg_pkv_scale; no bit but this one and
+ * the ACT bits -- else TMDNET_BAD_ARGUMENT, nothing launched, no output touched.  Width envelope: the vector
+ * form's (H = 32 V, V in {1, 2, 4, 8}, d / V a power of two; or H < 32 with H and d powers of two), else
+ * TMDNET_UNSUPPORTED, nothing launched.
+ * _bwd: outputs gq, gk, gv (leading dimensions of the inputs), gpk, gpv (per edge, for the pre-activation
+ * rows), gcut; each may be NULL (not wanted).  Rows [row_ptr[n_nodes], max_pairs) of gpk / gpv / gcut are
+ * written as zeros.  One launch: a wave serves its node as destination and, over the same row read as
+ * reversed edges, as source -- the vector form's PRECONDITION (a symmetric list with pk, pv, C equal on an
+ * edge and its reverse) holds here too.
+ * _bwd2: the VJP of that backward.  Cotangents gg_q, gg_k, gg_v, gg_pk, gg_pv, gg_cut (each nullable: zero;
+ * ld_gg* 0 = H); outputs d_grad_x, d_q, d_k, d_v, d_pk, d_pv, d_cut (each nullable: not wanted; ld_d* 0 = H),
+ * every row written, the padding rows of d_pk / d_pv / d_cut with zeros.  The per-edge cotangents are not
+ * pair-symmetric: the source sums read the reversed edge's rows through `transpose`, which is required
+ * (NULL: TMDNET_UNSUPPORTED); edge_scratch is not used.
+ * Every kernel: fp32 and fp64, one wave64 per destination row, every output written once, no atomics.
+ * n_nodes == 0 launches nothing (as in the vector form): the padding rows are then NOT written. */
+enum { TMDNET_ET_SCALAR = 0x10000 };
 /* Activations of the ET message entry points (tmdnet_et_message_fwd flags, _bwd accumulate, _bwd2
  * flags): bits 8-11 = the dk / dv projections' activation (reference EquivariantMultiHeadAttention
  * `activation`, torchmd_et.py:285-291), bits 12-15 = the attention activation (`attn_activation`,
@@ -269,6 +297,8 @@ int tmdnet_edge_geom_bwd(int dtype, int n_edges, int num_rbf, int rbf_type, cons
  *   two directions of a pair share one row (tmdnet_pair_index) and the projection GEMM runs over
  *   (E + N) / 2 rows instead of E.  Gradient outputs (gpk / gpv of the backward) stay per edge.
  * One wave64 per destination; outputs written once; no atomics; deterministic.
+ * With TMDNET_ET_SCALAR in flags (_bwd: in accumulate) the three entry points evaluate the invariant
+ * Transformer's message instead -- v, pv, x_out [.][H], no vector operands: see the comment at that enum.
  */
 int tmdnet_et_message_fwd(int dtype, int n_nodes, int hidden, int heads, const int32_t* row_ptr,
                           const int32_t* src, int max_pairs, const void* q, int ld_q, const void* k,

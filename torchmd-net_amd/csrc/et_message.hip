@@ -1924,6 +1924,30 @@ static int nb_setup(NbArgs<T>& A, int n, int H, const int32_t* row_ptr, const in
 
 using namespace tmd;
 
+// the scalar form of the three message entry points (t_message.hip), taken when a call carries
+// TMDNET_ET_SCALAR
+namespace tmd {
+int t_message_fwd(int dtype, int n, int H, int heads, const int32_t* row_ptr, const int32_t* src, int cap,
+                  const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* vec_in,
+                  const void* pk, int ldpk, const void* pv, int ldpv, const void* C, const void* unit, void* xo,
+                  void* vec_out, int flags, const int32_t* pk_rows, const int32_t* order, hipStream_t st);
+int t_message_bwd(int dtype, int n, int H, int heads, const int32_t* row_ptr, const int32_t* src, int cap,
+                  const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* vec_in,
+                  const void* pk, int ldpk, const void* pv, int ldpv, const void* C, const void* unit, const void* gx,
+                  const void* grad_vec, void* gq, void* gk, void* gv, void* gvec_in, void* gpk, void* gpv, void* gC,
+                  void* gunit, const void* dpk, const void* dpv, void* gdist, int flags, const int32_t* pk_rows,
+                  const int32_t* order, hipStream_t st);
+int t_message_bwd2(int dtype, int n, int H, int heads, const int32_t* row_ptr, const int32_t* src,
+                   const int32_t* transpose, int cap, const void* q, int ldq, const void* k, int ldk, const void* v,
+                   int ldv, const void* vec_in, const void* pk, int ldpk, const void* pv, int ldpv, const void* C,
+                   const void* unit, const void* gx, const void* grad_vec, const void* gg_q, int ld_ggq,
+                   const void* gg_k, int ld_ggk, const void* gg_v, int ld_ggv, const void* gg_vec, const void* gg_pk,
+                   int ld_ggpk, const void* gg_pv, int ld_ggpv, const void* gg_cut, const void* gg_unit,
+                   void* d_grad_x, void* d_grad_vec, void* d_q, int ld_dq, void* d_k, int ld_dk, void* d_v, int ld_dv,
+                   void* d_vec, void* d_pk, int ld_dpk, void* d_pv, int ld_dpv, void* d_cut, void* d_unit,
+                   const int32_t* pk_rows, const void* gg_pkv_scale, int flags, hipStream_t st);
+}  // namespace tmd
+
 extern "C" int tmdnet_et_message_fwd(int dtype, int n_nodes, int hidden, int heads,
                                      const int32_t* row_ptr, const int32_t* src, int max_pairs,
                                      const void* q, int ld_q, const void* k, int ld_k, const void* v,
@@ -1932,6 +1956,9 @@ extern "C" int tmdnet_et_message_fwd(int dtype, int n_nodes, int hidden, int hea
                                      void* x_out, void* vec_out, int flags, const int32_t* pk_rows,
                                      const int32_t* order, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  if (flags & TMDNET_ET_SCALAR)
+    return t_message_fwd(dtype, n_nodes, hidden, heads, row_ptr, src, max_pairs, q, ld_q, k, ld_k, v, ld_v, vec_in,
+                         pk, ld_pk, pv, ld_pv, cutoff, unit, x_out, vec_out, flags, pk_rows, order, st);
   if (dtype == TMDNET_F32)
     return et::fwd<float>(n_nodes, hidden, heads, row_ptr, src, max_pairs, q, ld_q, k, ld_k, v, ld_v,
                           vec_in, pk, ld_pk, pv, ld_pv, cutoff, unit, x_out, vec_out, flags, pk_rows, order, st);
@@ -1953,6 +1980,10 @@ extern "C" int tmdnet_et_message_bwd(int dtype, int n_nodes, int hidden, int hea
                                      int accumulate, const int32_t* pk_rows, const int32_t* order,
                                      void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  if (accumulate & TMDNET_ET_SCALAR)
+    return t_message_bwd(dtype, n_nodes, hidden, heads, row_ptr, src, max_pairs, q, ld_q, k, ld_k, v, ld_v, vec_in,
+                         pk, ld_pk, pv, ld_pv, cutoff, unit, grad_x, grad_vec, gq, gk, gv, gvec_in, gpk, gpv, gcut,
+                         gunit, dpk, dpv, gdist, accumulate, pk_rows, order, st);
   if (dtype == TMDNET_F32)
     return et::bwd<float>(n_nodes, hidden, heads, row_ptr, src, max_pairs, q, ld_q, k, ld_k, v, ld_v,
                           vec_in, pk, ld_pk, pv, ld_pv, cutoff, unit, grad_x, grad_vec, gq, gk, gv,
@@ -1975,6 +2006,12 @@ extern "C" int tmdnet_et_message_bwd2(
     void* d_v, int ld_dv, void* d_vec, void* d_pk, int ld_dpk, void* d_pv, int ld_dpv, void* d_cut,
     void* d_unit, void* edge_scratch, const int32_t* pk_rows, const void* gg_pkv_scale, int flags, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  if (flags & TMDNET_ET_SCALAR)  // (edge_scratch is not used: the source role reads through `transpose`)
+    return t_message_bwd2(dtype, n_nodes, hidden, heads, row_ptr, src, transpose, max_pairs, q, ld_q, k, ld_k, v,
+                          ld_v, vec_in, pk, ld_pk, pv, ld_pv, cutoff, unit, grad_x, grad_vec, gg_q, ld_ggq, gg_k,
+                          ld_ggk, gg_v, ld_ggv, gg_vec, gg_pk, ld_ggpk, gg_pv, ld_ggpv, gg_cut, gg_unit, d_grad_x,
+                          d_grad_vec, d_q, ld_dq, d_k, ld_dk, d_v, ld_dv, d_vec, d_pk, ld_dpk, d_pv, ld_dpv, d_cut,
+                          d_unit, pk_rows, gg_pkv_scale, flags, st);
   const et::Bwd2Ex ex{ld_ggq, ld_ggk, ld_ggv, ld_dq, ld_dk, ld_dv, ld_dpk, ld_dpv, transpose, edge_scratch, pk_rows,
                       gg_pkv_scale};
   // no stride, no source-pass scratch, no pair rows: the dense form, which makes no use of the record

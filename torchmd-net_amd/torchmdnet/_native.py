@@ -25,6 +25,7 @@ ET_V_PLANAR = 4
 BWD2_ACC_EDGE, BWD2_ACC_GVEC = 8, 16
 ET_TWO_PASS = 64
 ET_PREACT = 128  # pk / pv (dpk / dpv) hold the activated rows S (D) of tmdnet_proj_act_f32
+ET_SCALAR = 0x10000  # the message entry points' scalar form (the invariant Transformer's message)
 
 UNSUPPORTED = 2  # TMDNET_UNSUPPORTED: outside an entry point's envelope, nothing launched
 

@@ -1507,6 +1507,187 @@ def et_message(q, k, v, vec, pk, pv, C, u, graph, heads, acts=0):
     return _ETMessage.apply(q, k, v, vec.contiguous(), pk, pv, C.contiguous(), u.contiguous(), graph, heads, acts)
 
 
+# ----------------------------------------------------------------------------- Transformer message
+def t_message_composite(q, k, v, pk, pv, C, src, dst, n_nodes, heads, acts=0):
+    """PyTorch restatement of the invariant Transformer's message + aggregation (reference
+    torchmd_t.py:246-283; CPU tensors and the third-order fallback): the ET message without the vector
+    channels.  ``pk`` / ``pv``: pre-activation dk / dv rows [E, H] or None (factor 1); slots with
+    ``src < 0`` are padding and carry nothing; ``acts``: et_act_flags(activation, attn_activation)."""
+    act_kv, act_at = et_act_fns(acts)
+    H = q.shape[1]
+    d = H // heads
+    valid = (src >= 0).to(q.dtype)
+    src, dst = src.clamp(min=0), dst.clamp(min=0)
+    s = q.index_select(0, dst).view(-1, heads, d) * k.index_select(0, src).view(-1, heads, d)
+    if pk is not None:
+        s = s * act_kv(pk).view(-1, heads, d)
+    attn = act_at(s.sum(-1)) * (C * valid).unsqueeze(1)
+    vj = v.index_select(0, src).view(-1, heads, d)
+    if pv is not None:
+        vj = vj * act_kv(pv).view(-1, heads, d)
+    out = torch.zeros((n_nodes, heads, d), dtype=q.dtype, device=q.device).index_add(0, dst, vj * attn.unsqueeze(2))
+    return out.view(n_nodes, H)
+
+
+def _t_rows(t, width):
+    """Rows the scalar message kernels can read in place: unit element stride, a row stride of at least the
+    width (column blocks of a wider buffer qualify)."""
+    if t is not None and (t.stride(-1) != 1 or t.stride(0) < width):
+        t = t.contiguous()
+    return t
+
+
+def _t_column_blocks(pk, pv):
+    """Are pk and pv the two column blocks of one [E, 2H] buffer?"""
+    if pk is None or pv is None:
+        return False
+    H = pk.shape[1]
+    return (pk.stride(0) == 2 * H and pv.stride(0) == 2 * H
+            and pv.data_ptr() == pk.data_ptr() + H * pk.element_size())
+
+
+def _t_check_graph(graph):
+    if not graph.symmetric or graph.transpose is None:
+        raise RuntimeError("torchmd-net_amd: the Transformer message backward needs a symmetric edge list "
+                           "(include_transpose=True, no capacity overflow)")
+
+
+def _t_wanted(ctx, tensors):
+    """Per leading input of a Function's backward: does something consume its gradient?  (``next_functions`` has
+    one entry per TENSOR input: an absent operand, None, has none.)"""
+    nodes = iter(ctx.next_functions)
+    want = []
+    for i, t in enumerate(tensors):
+        node = None if t is None else next(nodes)[0]
+        want.append(t is not None and bool(ctx.needs_input_grad[i]) and _will_run(node))
+    return tuple(want)
+
+
+class _TMessage(Function):
+    """out = t_message(q, k, v, pk, pv, C): tmdnet_et_message_fwd in its scalar form (TMDNET_ET_SCALAR)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, pk, pv, C, graph, heads, acts):
+        N, H = q.shape
+        out = torch.empty((N, H), dtype=q.dtype, device=q.device)
+        P = nat.ptr
+        rc = nat.load().tmdnet_et_message_fwd(
+            nat.dtype_code(q.dtype), N, H, heads, P(graph.row_ptr), P(graph.src), graph.n_edges, P(q), _ld(q),
+            P(k), _ld(k), P(v), _ld(v), None, P(pk), _ld(pk), P(pv), _ld(pv), P(C), None, P(out), None,
+            int(acts) | nat.ET_SCALAR, None, None, nat.stream(q.device))
+        nat.check(rc, "tmdnet_et_message_fwd")
+        ctx.graph, ctx.heads, ctx.acts = graph, heads, acts
+        ctx.save_for_backward(q, k, v, pk, pv, C)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        q, k, v, pk, pv, C = ctx.saved_tensors
+        # a gradient only where something consumes it
+        want = _t_wanted(ctx, (q, k, v, pk, pv, C))
+        gs = _TMessageBwd.apply(gout.contiguous(), q, k, v, pk, pv, C, ctx.graph, ctx.heads, ctx.acts, want)
+        return tuple(g if w else None for g, w in zip(gs, want)) + (None, None, None)
+
+
+class _TMessageBwd(Function):
+    """(gq, gk, gv, gpk, gpv, gC) of t_message: tmdnet_et_message_bwd in its scalar form, one launch.  Its
+    backward is tmdnet_et_message_bwd2 (scalar form); building a third order runs autograd over the
+    composite."""
+
+    @staticmethod
+    def forward(ctx, gout, q, k, v, pk, pv, C, graph, heads, acts, want=(True,) * 6):
+        _t_check_graph(graph)
+        N, H = q.shape
+        E = graph.n_edges
+        # every row is written by the kernel (static-capacity padding rows with zeros): no fill
+        gq = rows_like(q) if want[0] else None
+        gk = rows_like(k) if want[1] else None
+        gv = rows_like(v) if want[2] else None
+        if _t_column_blocks(pk, pv) and want[3] and want[4]:
+            # pk | pv are the column blocks of one [E, 2H] buffer: so are their gradients
+            gpkv = torch.empty((E, 2 * H), dtype=q.dtype, device=q.device)
+            gpk, gpv = gpkv[:, :H], gpkv[:, H:]
+        else:
+            gpk = rows_like(pk) if (pk is not None and want[3]) else None
+            gpv = rows_like(pv) if (pv is not None and want[4]) else None
+        gC = torch.empty((E,), dtype=q.dtype, device=q.device) if want[5] else None
+        P = nat.ptr
+        rc = nat.load().tmdnet_et_message_bwd(
+            nat.dtype_code(q.dtype), N, H, heads, P(graph.row_ptr), P(graph.src), E, P(q), _ld(q), P(k), _ld(k),
+            P(v), _ld(v), None, P(pk), _ld(pk), P(pv), _ld(pv), P(C), None, P(gout), None, P(gq), P(gk), P(gv),
+            None, P(gpk), P(gpv), P(gC), None, None, None, None, int(acts) | nat.ET_SCALAR, None, None,
+            nat.stream(q.device))
+        nat.check(rc, "tmdnet_et_message_bwd")
+        ctx.graph, ctx.heads, ctx.acts = graph, heads, acts
+        ctx.save_for_backward(gout, q, k, v, pk, pv, C)
+        return gq, gk, gv, gpk, gpv, gC
+
+    @staticmethod
+    def backward(ctx, ggq, ggk, ggv, ggpk, ggpv, ggC):
+        gout, q, k, v, pk, pv, C = ctx.saved_tensors
+        graph, heads, acts = ctx.graph, ctx.heads, ctx.acts
+        ggs = (ggq, ggk, ggv, ggpk if pk is not None else None, ggpv if pv is not None else None, ggC)
+        _create = torch.is_grad_enabled()  # third order only if the caller builds a graph
+        if not _create:
+            want = _t_wanted(ctx, (gout, q, k, v, pk, pv, C))
+            if not any(want) or all(g is None for g in ggs):
+                return (None,) * 11
+            N, H = q.shape
+            E = graph.n_edges
+            o = dict(dtype=q.dtype, device=q.device)
+            d_go = torch.empty((N, H), **o) if want[0] else None
+            d_q = torch.empty((N, H), **o) if want[1] else None
+            d_k = torch.empty((N, H), **o) if want[2] else None
+            d_v = torch.empty((N, H), **o) if want[3] else None
+            d_pk = torch.empty((E, H), **o) if (pk is not None and want[4]) else None
+            d_pv = torch.empty((E, H), **o) if (pv is not None and want[5]) else None
+            d_C = torch.empty((E,), **o) if want[6] else None
+            gq_, gk_, gv_, gpk_, gpv_ = (_t_rows(g, H) for g in ggs[:5])
+            gC_ = None if ggC is None else ggC.contiguous()
+            P = nat.ptr
+            rc = nat.load().tmdnet_et_message_bwd2(
+                nat.dtype_code(q.dtype), N, H, heads, P(graph.row_ptr), P(graph.src), P(graph.transpose), E,
+                P(q), _ld(q), P(k), _ld(k), P(v), _ld(v), None, P(pk), _ld(pk), P(pv), _ld(pv), P(C), None,
+                P(gout), None, P(gq_), _ld(gq_), P(gk_), _ld(gk_), P(gv_), _ld(gv_), None, P(gpk_), _ld(gpk_),
+                P(gpv_), _ld(gpv_), P(gC_), None, P(d_go), None, P(d_q), 0, P(d_k), 0, P(d_v), 0, None, P(d_pk), 0,
+                P(d_pv), 0, P(d_C), None, None, None, None, int(acts) | nat.ET_SCALAR, nat.stream(q.device))
+            nat.check(rc, "tmdnet_et_message_bwd2")
+            return d_go, d_q, d_k, d_v, d_pk, d_pv, d_C, None, None, None, None
+        src, dst = graph.src.long(), graph.dst.long()
+        with torch.enable_grad():
+            leaves = [None if t is None else t.detach().requires_grad_(True) for t in (gout, q, k, v, pk, pv, C)]
+            go, q_, k_, v_, pk_, pv_, C_ = leaves
+            out = t_message_composite(q_, k_, v_, pk_, pv_, C_, src, dst, graph.n_nodes, heads, acts)
+            wrt = (q_, k_, v_, pk_, pv_, C_)
+            first = torch.autograd.grad(out, [t for t in wrt if t is not None], go, create_graph=True)
+            it = iter(first)
+            first = [next(it) if t is not None else None for t in wrt]
+            sel = [(f, g) for f, g in zip(first, ggs) if f is not None and g is not None]
+            if not sel:
+                return (None,) * 11
+            ins = [t for t in leaves if t is not None]
+            second = torch.autograd.grad([f for f, _ in sel], ins, [g for _, g in sel], create_graph=True,
+                                         allow_unused=True)
+        it = iter(second)
+        return tuple(next(it) if t is not None else None for t in leaves) + (None, None, None, None)
+
+
+def t_message(q, k, v, pk, pv, C, graph, heads, acts=0):
+    """The invariant Transformer's message + aggregation over the CSR ``graph`` (reference torchmd_t.py:246-283):
+    ``out[t] = sum_{e in row t} v[s] A(pv[e]) B(sum_c q[t] k[s] A(pk[e])) C[e]`` per head.  ``pk`` / ``pv``
+    are the pre-activation dk / dv rows (None: factor 1; they may be column blocks of one [E, 2H] buffer),
+    ``acts`` = et_act_flags(activation, attn_activation).  GPU tensors run the scalar form of the ET message
+    entry points (forward, backward and second order, no atomics); CPU tensors the composite."""
+    if not q.is_cuda:
+        return t_message_composite(q, k, v, pk, pv, C, graph.src.long(), graph.dst.long(), graph.n_nodes, heads,
+                                   acts)
+    H = q.shape[1]
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, pk, pv, C)):
+        _t_check_graph(graph)
+    q, k, v, pk, pv = (_t_rows(t, H) for t in (q, k, v, pk, pv))
+    return _TMessage.apply(q, k, v, pk, pv, C.contiguous(), graph, heads, acts)
+
+
 # ----------------------------------------------------------------------------- neighbour embedding
 def nbr_embed_composite(x, w, C, src, dst, n_nodes):
     keep = ((src != dst) & (src >= 0)).to(x.dtype).unsqueeze(1)

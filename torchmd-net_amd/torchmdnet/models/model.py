@@ -18,7 +18,8 @@ from .utils import dtype_mapping
 from .. import priors
 
 
-def create_model(args, prior_model=None, mean=None, std=None):
+def _compute_dtype(args):
+    """(dtype the model computes in, float16 storage?) of the argument dict's ``precision``."""
     dtype = dtype_mapping[args["precision"]]
     # precision 16 (reference dtype_mapping[16] = float16, models/utils.py:586): parameters and buffers are
     # STORED in float16 (the reference's state_dict dtype), the hot path computes in float32 on upcast copies
@@ -28,7 +29,11 @@ def create_model(args, prior_model=None, mean=None, std=None):
         dtype = torch.float32
     if dtype not in (torch.float32, torch.float64):
         raise NotImplementedError("torchmd-net_amd computes in float32 or float64 (precision 16/32/64)")
-    shared_args = dict(
+    return dtype, half
+
+
+def _shared_args(args, dtype):
+    return dict(
         hidden_channels=args["embedding_dimension"],
         num_layers=args["num_layers"],
         num_rbf=args["num_rbf"],
@@ -41,6 +46,11 @@ def create_model(args, prior_model=None, mean=None, std=None):
         max_num_neighbors=args["max_num_neighbors"],
         dtype=dtype,
     )
+
+
+def create_model(args, prior_model=None, mean=None, std=None):
+    dtype, half = _compute_dtype(args)
+    shared_args = _shared_args(args, dtype)
     if args["model"] == "equivariant-transformer":
         from .torchmd_et import TorchMD_ET
 
@@ -71,10 +81,34 @@ def create_model(args, prior_model=None, mean=None, std=None):
             **shared_args,
         )
     elif args["model"] == "transformer":
-        raise NotImplementedError(f'{args["model"]} is outside the MI355X hot path (ET, TensorNet, graph-network)')
+        raise NotImplementedError(f'{args["model"]}: build the Transformer with create_transformer_model(args) '
+                                  "(create_model assembles ET, TensorNet and graph-network)")
     else:
         raise ValueError(f'Unknown architecture: {args["model"]}')
+    return _assemble(args, representation_model, is_equivariant, dtype, half, prior_model, mean, std)
 
+
+def create_transformer_model(args, prior_model=None, mean=None, std=None):
+    """The reference's ``create_model`` for ``model: transformer`` (model.py:59-70): TorchMD_T under the same
+    atom filter, priors, head and TorchMD_Net as the other architectures."""
+    if args["model"] != "transformer":
+        raise ValueError(f'create_transformer_model builds "transformer" models, not {args["model"]!r} '
+                         "(use create_model)")
+    from .torchmd_t import TorchMD_T
+
+    dtype, half = _compute_dtype(args)
+    representation_model = TorchMD_T(
+        attn_activation=args["attn_activation"],
+        num_heads=args["num_heads"],
+        distance_influence=args["distance_influence"],
+        neighbor_embedding=args["neighbor_embedding"],
+        **_shared_args(args, dtype),
+    )
+    return _assemble(args, representation_model, False, dtype, half, prior_model, mean, std)
+
+
+def _assemble(args, representation_model, is_equivariant, dtype, half, prior_model, mean, std):
+    """Everything ``create_model`` does once the representation model is chosen."""
     # atom filter (reference model.py:88-92): the wrapped model runs eagerly (models/wrappers.py)
     if args.get("atom_filter", -1) > -1:
         if args["derivative"]:
@@ -107,7 +141,7 @@ def load_model(filepath, args=None, device="cpu", **kwargs):
         if key not in args:
             warnings.warn(f"Unknown hyperparameter: {key}={value}")
         args[key] = value
-    model = create_model(args)
+    model = create_transformer_model(args) if args["model"] == "transformer" else create_model(args)
     state_dict = {re.sub(r"^model\.", "", k): v for k, v in ckpt["state_dict"].items()}
     if "prior_model.initial_atomref" in state_dict:
         state_dict["prior_model.0.initial_atomref"] = state_dict.pop("prior_model.initial_atomref")
